@@ -16,7 +16,16 @@ N > 1 either launch it under torch.distributed.run (RANK/WORLD_SIZE set), or run
 parent then starts `torch.distributed.run --nproc-per-node N` as a child process before any GPU
 call of its own, forwards rank 0's JSON line and exits with the children's status.  A box with
 fewer GPUs than ranks rehearses over gloo (ranks share devices; config.rehearsal says so).
-Extra keys:
+
+A plain run sets up, runs W untimed and K timed steps, and prints the line: metric, value, unit,
+higher_is_better, dtype, ms_per_step (one timed step), config, host_issue_us_per_step; at N > 1
+it times the first halo source that works.  `--dump-outputs DIR` also writes what the last timed
+step computed as DIR/<name>.npy (float32 for 8-bit outputs, else float64; a fixed, seeded sample
+of an output too large for the 64 MB limit; the inputs are seeded, so two builds can be compared
+file by file).  Everything else runs only with `--full`, after the timed steps, and adds its
+keys to the line: the roofline loop, the parity check, the CPU baselines, the other configs
+('configs'), and at N > 1 every halo leg, the hand-off's own cost and strong scaling.
+Extra keys with --full:
   roofline      dominant kernel's algorithmic bytes / its mean duration (HIP events on the
                 stream it runs on: 100 untimed ramp launches and >= 50 ms of them, then 200 timed back to back,
                 whatever --steps/--warmup are), vs the 8.0 TB/s HBM3E peak; `traffic` = PMC
@@ -556,6 +565,39 @@ class Workload:
             return bool(np.array_equal(got, ref))
         return fir_hip.metrics_from_sums(got, self.n) == ref
 
+    def outputs(self) -> dict:
+        """What the last step handed its caller, by name (device tensors): ``y`` (``y_rank<r>`` at
+        N > 1), or pipeline_fixed3's 28 planes ``<image>_<filter>`` of the buffer set that step
+        wrote."""
+        if self.name == "pipeline_fixed3":
+            _, ys = self.sets[(self.turn - 1) % len(self.sets)]
+            return {f"{stem}_{BANK3_NAMES[f]}": ys[k][f] for k, (stem, _) in enumerate(self.images)
+                    for f in range(len(BANK3))}
+        return {"y" if self.world == 1 else f"y_rank{self.rank}": self.y}
+
+
+DUMP_BUDGET = 48 << 20  # bytes of .npy data --dump-outputs writes per rank (the limit is 64 MB in all)
+
+
+def dump_outputs(wl: Workload, out_dir: Path) -> None:
+    """--dump-outputs: every output of ``wl.outputs()`` as ``out_dir/<name>.npy``, float32 for
+    8-bit outputs and float64 for the others (both exact).  An output larger than its share of
+    DUMP_BUDGET is sampled, the same elements in every run and build: the first and the last
+    quarter of the share and, between them, sorted indices drawn from default_rng(SEED)."""
+    outs = wl.outputs()
+    out_dir.mkdir(parents=True, exist_ok=True)
+    share = DUMP_BUDGET // max(1, wl.world) // len(outs)
+    for name, t in outs.items():
+        flat = t.reshape(-1)
+        to = torch.float32 if flat.element_size() == 1 else torch.float64
+        keep = share // (4 if to == torch.float32 else 8)
+        if flat.numel() > keep:
+            edge = keep // 4
+            mid = np.random.default_rng(SEED).choice(flat.numel() - 2 * edge, keep - 2 * edge, replace=False)
+            idx = np.concatenate([np.arange(edge), np.sort(mid) + edge, np.arange(flat.numel() - edge, flat.numel())])
+            flat = flat[torch.from_numpy(idx).to(flat.device)]
+        np.save(out_dir / f"{name}.npy", flat.to(to).cpu().numpy())
+
 
 RAMP_MS = 50.0  # the roofline loop's untimed ramp lasts at least this much GPU time
 
@@ -581,13 +623,15 @@ def ramp_launches(wl: Workload, at_least: int, world: int = 1, red_dev=None) -> 
 
 
 def measure(wl: Workload, steps: int, warmup: int, ramp: int, launches: int, world: int = 1,
-            barrier=lambda: None, red_dev=None):
+            barrier=lambda: None, red_dev=None, full: bool = True, after=None):
     """Time ``steps`` steps after ``warmup`` untimed ones (barrier + synchronize on both sides, max
     over ranks), then the dominant kernel alone: ``ramp`` untimed launches and at least RAMP_MS of
     them (ramp_launches), then ``launches`` back to back on the stream it runs on, bracketed by
     two HIP events (events between launches would perturb the stream: each record adds a ~11 us
     gap).  Leaves the full step's output in place.  Returns (elapsed s, host issue s, mean
-    dominant-kernel s)."""
+    dominant-kernel s).  ``after`` (--dump-outputs) is called once the timed steps are done, while
+    the last timed step's output is in place; ``full=False`` (a plain run) stops there and returns
+    None for the dominant kernel."""
     for _ in range(warmup):
         wl.step()
     barrier()
@@ -603,6 +647,10 @@ def measure(wl: Workload, steps: int, warmup: int, ramp: int, launches: int, wor
         t = torch.tensor([elapsed], dtype=torch.float64, device=red_dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if after is not None:
+        after()
+    if not full:
+        return elapsed, t_issue, None
     kern_avg_s = roofline_loop(wl, ramp, launches, world, red_dev)
     wl.step()  # restore the full step's output (the loop above ran the dominant kernel alone)
     torch.cuda.synchronize()
@@ -704,8 +752,8 @@ def pmc_traffic(wl: Workload, root: Path = ROOT):
     return summary.get("hbm_bytes_per_launch")
 
 
-# The other single-GPU BASELINE configs, timed after the headline when bench.py runs without
-# --workload at N = 1 (the driver's own run): configs[2] complex int16 2^27, configs[4] fir_2d 5x5
+# The other single-GPU BASELINE configs, timed after the headline when bench.py --full runs without
+# --workload at N = 1: configs[2] complex int16 2^27, configs[4] fir_2d 5x5
 # on 8192^2 frames, configs[0] the pipeline's fixed 3-tap stage on the 7 golden images.
 SUB_CONFIGS = (("configs[2]", "cplx_i16"), ("configs[4]", "fir2d_u8"), ("configs[0]", "pipeline_fixed3"))
 
@@ -832,11 +880,13 @@ def run_halo_legs(kinds, run_one) -> tuple[dict, str | None]:
     return legs, (ok[0] if ok else None)
 
 
-def halo_leg(wl: Workload, kind: str, args, world: int, barrier, red_dev, parity_check: bool = True) -> dict:
+def halo_leg(wl: Workload, kind: str, args, world: int, barrier, red_dev, parity_check: bool = True,
+             full: bool = True, after=None) -> dict:
     """One N > 1 leg: set up ``kind``'s halo source over the resident segments (xGMI: mapped
     mailboxes, probed collectively; rccl: the send/recv exchange), time the steps and the dominant
     kernel, report the hand-off's own cost, check every rank's full output against the oracle,
-    and release the source.  Raises LegFailed when the source cannot run."""
+    and release the source.  Raises LegFailed when the source cannot run.  ``full=False`` (a plain
+    run) times the steps only; ``after`` is measure()'s."""
     if kind == "xgmi":
         got, src = sharded.make_halo_source(wl.x, wl.taps.n, wl.channels, prefer="xgmi")
         if got != "xgmi":
@@ -847,12 +897,17 @@ def halo_leg(wl: Workload, kind: str, args, world: int, barrier, red_dev, parity
     try:
         barrier()
         elapsed, t_issue, kern = measure(wl, args.steps, args.warmup, args.roofline_ramp, args.roofline_launches,
-                                         world, barrier, red_dev)
-        kern_ranks = gather_floats(kern, world, red_dev)
+                                         world, barrier, red_dev, full=full, after=after)
+        kern_ranks = gather_floats(kern, world, red_dev) if full else None
         failed = gate_failures(wl, world, red_dev)
         if failed:
             raise LegFailed(f"halo gate timed out (a neighbour's epoch did not arrive within {src.timeout_s} s) on "
                             f"rank(s) {failed}")
+        units = gather_floats(float(wl.units), world, red_dev)
+        if not full:
+            return {"value": round(sum(units) * args.steps / elapsed / 1e9, 3), "unit": wl.unit,
+                    "ms_per_step": round(elapsed / args.steps * 1e3, 4), "parity": "skipped",
+                    "parallelism": wl.config["parallelism"], "_elapsed": elapsed, "_t_issue": t_issue}
         halo = halo_report(wl, world, barrier, red_dev)
         parity = "skipped"
         if parity_check:
@@ -860,7 +915,6 @@ def halo_leg(wl: Workload, kind: str, args, world: int, barrier, red_dev, parity
             f = torch.tensor([0 if ok else 1], device=red_dev)
             dist.all_reduce(f, op=dist.ReduceOp.MAX)
             parity = "bit-exact vs oracle (full output, every rank)" if int(f.item()) == 0 else "MISMATCH"
-        units = gather_floats(float(wl.units), world, red_dev)
         return {"value": round(sum(units) * args.steps / elapsed / 1e9, 3), "unit": wl.unit,
                 "ms_per_step": round(elapsed / args.steps * 1e3, 4),
                 "kernel_avg_us_ranks": {"max": round(max(kern_ranks) * 1e6, 2), "min": round(min(kern_ranks) * 1e6, 2)},
@@ -875,24 +929,33 @@ def halo_leg(wl: Workload, kind: str, args, world: int, barrier, red_dev, parity
 def main() -> int:
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=200)
+    ap.add_argument("--steps", type=int, default=200, help="timed steps")
     ap.add_argument("--warmup", type=int, default=100, help="untimed steps (clocks take ~40 launches to ramp)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the roofline loop, the oracle parity check, the CPU "
+                         "baselines, the other configs and, at N > 1, every halo leg, the hand-off's own cost "
+                         "and strong scaling (the options below narrow these; a plain run does none of them)")
+    ap.add_argument("--dump-outputs", type=Path, default=None, metavar="DIR",
+                    help="write what the last timed step computed as DIR/<name>.npy (float32 / float64, a "
+                         "fixed seeded sample of a large output)")
     ap.add_argument("--workload", default=None, choices=tuple(KERNELS),
-                    help="default fir1d_i16 (configs[1]); without this flag an N = 1 run also times "
+                    help="default fir1d_i16 (configs[1]); without this flag an N = 1 --full run also times "
                          "configs[2], [4] and [0] (the line's 'configs' key)")
-    ap.add_argument("--no-configs", action="store_true", help="time the headline workload only")
+    ap.add_argument("--no-configs", action="store_true", help="--full: time the headline workload only")
     ap.add_argument("--log2n", type=int, default=28, help="int16 values per GPU (2^28 = BASELINE configs[1])")
-    ap.add_argument("--cpu-seconds", type=float, default=10.0, help="CPU-baseline time budget (0 = skip)")
-    ap.add_argument("--no-parity", action="store_true", help="skip the full-size oracle comparison")
+    ap.add_argument("--cpu-seconds", type=float, default=10.0, help="--full: CPU-baseline time budget (0 = skip)")
+    ap.add_argument("--no-parity", action="store_true", help="--full: skip the full-size oracle comparison")
     ap.add_argument("--roofline-launches", type=int, default=ROOF_LAUNCHES,
-                    help="timed launches of the dominant kernel (after as many as --roofline-ramp untimed)")
+                    help="--full: timed launches of the dominant kernel (after as many as --roofline-ramp untimed)")
     ap.add_argument("--roofline-ramp", type=int, default=ROOF_RAMP)
     args = ap.parse_args()
-    sub_configs = args.workload is None and not args.no_configs and not SELF_HALO
+    sub_configs = args.full and args.workload is None and not args.no_configs and not SELF_HALO
     args.workload = args.workload or "fir1d_i16"
 
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1:
+        raise SystemExit("--steps must be >= 1")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # started directly: spawn the ranks as children (nothing here has touched the GPU;
         # device_count() does not initialise it on this image)
@@ -946,13 +1009,23 @@ def main() -> int:
                 dist.barrier()
 
     barrier()  # every rank's segment is resident and its communicator up before the first step
-    legs = strong = None
+    dump = (lambda: dump_outputs(wl, args.dump_outputs)) if args.dump_outputs is not None else None
+    legs = strong = kern_avg_s = kern_ranks = halo = None
     if wl.sharded_1d and world > 1:
         # both halo sources, each its own leg with its own numbers (the first real multi-GPU run
-        # then yields a value whichever source works); the headline is the first that worked
+        # then yields a value whichever source works); the headline is the first that worked.
+        # A plain run stops at the first source that works and times its steps only.
         kinds = ["xgmi", "rccl"] if HALO_PREF == "xgmi" else [HALO_PREF]
-        legs, head = run_halo_legs(kinds, lambda k: halo_leg(wl, k, args, world, barrier, red_dev,
-                                                             not args.no_parity))
+
+        def run_one(k):
+            return halo_leg(wl, k, args, world, barrier, red_dev, not args.no_parity, full=args.full, after=dump)
+
+        legs, head = {}, None
+        for group in ([kinds] if args.full else [[k] for k in kinds]):
+            done, head = run_halo_legs(group, run_one)
+            legs.update(done)
+            if head is not None:
+                break
         if head is None:
             if rank == 0:
                 emit_result(json.dumps({"metric": METRIC, "value": None, "unit": wl.unit, "n_gpus": world,
@@ -962,32 +1035,33 @@ def main() -> int:
             dist.destroy_process_group()
             return 3
         lead = legs[head]
-        elapsed, t_issue, kern_avg_s = lead["_elapsed"], lead["_t_issue"], lead["_kern"]
-        kern_ranks = [lead["kernel_avg_us_ranks"]["max"] / 1e6, lead["kernel_avg_us_ranks"]["min"] / 1e6]
-        halo, parity = lead["halo"], lead["parity"]
+        elapsed, t_issue, parity = lead["_elapsed"], lead["_t_issue"], lead["parity"]
         wl.config["parallelism"] = lead["parallelism"]
-        # strong scaling beside the weak headline: the same total as one GPU's headline (2^log2n
-        # samples) split over the N ranks, through the headline's halo source
-        swl = Workload(args.workload, rank, world, dev, args.log2n, n_total=1 << args.log2n)
-        torch.cuda.synchronize()
-        try:
-            srec = halo_leg(swl, head, args, world, barrier, red_dev, not args.no_parity)
-            spans = gather_floats(float(swl.n), world, red_dev)
-            strong = {"total_samples": 1 << args.log2n, "samples_per_rank": {"max": int(max(spans)),
-                                                                              "min": int(min(spans))},
-                      **{k: v for k, v in srec.items() if not k.startswith("_") and k != "parallelism"},
-                      "scaling": "strong", "halo_source": head}
-        except LegFailed as exc:
-            strong = {"total_samples": 1 << args.log2n, "error": str(exc), "halo_source": head}
-        del swl
+        if args.full:
+            kern_avg_s, halo = lead["_kern"], lead["halo"]
+            kern_ranks = [lead["kernel_avg_us_ranks"]["max"] / 1e6, lead["kernel_avg_us_ranks"]["min"] / 1e6]
+            # strong scaling beside the weak headline: the same total as one GPU's headline (2^log2n
+            # samples) split over the N ranks, through the headline's halo source
+            swl = Workload(args.workload, rank, world, dev, args.log2n, n_total=1 << args.log2n)
+            torch.cuda.synchronize()
+            try:
+                srec = halo_leg(swl, head, args, world, barrier, red_dev, not args.no_parity)
+                spans = gather_floats(float(swl.n), world, red_dev)
+                strong = {"total_samples": 1 << args.log2n, "samples_per_rank": {"max": int(max(spans)),
+                                                                                  "min": int(min(spans))},
+                          **{k: v for k, v in srec.items() if not k.startswith("_") and k != "parallelism"},
+                          "scaling": "strong", "halo_source": head}
+            except LegFailed as exc:
+                strong = {"total_samples": 1 << args.log2n, "error": str(exc), "halo_source": head}
+            del swl
         for rec in legs.values():
             for k in [k for k in rec if k.startswith("_")]:
                 del rec[k]
     else:
         elapsed, t_issue, kern_avg_s = measure(wl, args.steps, args.warmup, args.roofline_ramp,
-                                               args.roofline_launches, world, barrier, red_dev)
-        kern_ranks = gather_floats(kern_avg_s, world, red_dev)
-        halo = None
+                                               args.roofline_launches, world, barrier, red_dev,
+                                               full=args.full, after=dump)
+        kern_ranks = gather_floats(kern_avg_s, world, red_dev) if args.full else None
         failed = gate_failures(wl, world, red_dev) if wl.sharded_1d else []
         if failed:
             if rank == 0:
@@ -1001,7 +1075,7 @@ def main() -> int:
             return 3
         # parity: full output vs the C oracle (every rank, its own segment with the received halos)
         parity = "skipped"
-        if not args.no_parity:
+        if args.full and not args.no_parity:
             ok = wl.matches(wl.oracle(_cpu_threads()))
             if world > 1:
                 f = torch.tensor([0 if ok else 1], device=red_dev)
@@ -1012,7 +1086,7 @@ def main() -> int:
 
     # CPU legs: rank 0 only, at every N, after the GPU legs (the other ranks wait at the barrier below)
     cpu = cpu_np = cpu_np_mt = cpu_loop = None
-    if rank == 0 and args.cpu_seconds > 0:
+    if rank == 0 and args.full and args.cpu_seconds > 0:
         nthr = _cpu_threads()
         wl.oracle(nthr)  # warm (page-in, thread pool)
         reps, tc0 = 0, time.perf_counter()
@@ -1056,12 +1130,8 @@ def main() -> int:
 
     barrier()  # rank 0's CPU legs are done
 
-    traffic = pmc_traffic(wl)
-
     total_units = wl.units * world * args.steps
     value = total_units / elapsed / 1e9
-    alg_bytes = wl.alg_bytes
-    achieved = alg_bytes / kern_avg_s / 1e9
     line = {
         "metric": METRIC if args.workload == "fir1d_i16" else f"{wl.unit}, {wl.config['workload']}",
         "value": round(value, 3),
@@ -1076,28 +1146,34 @@ def main() -> int:
         "dtype": wl.dtype,
         "data": "synthetic (numpy default_rng seed 20260227 + rank), resident in HBM before timing",
         "config": wl.config,
-        "roofline": {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                     "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic,
-                     "kernel": "fir2d_mfma_kernel" if wl.gen2d else KERNELS[args.workload],
-                     "limiter": ("HBM (int8 MFMA Toeplitz rows, 32-row strips walking alternately down and up; "
-                                 "PMC 1.008x, DESIGN.md §5)" if wl.gen2d else
-                                 "HBM (separable packed-16 strips; alternate strips walk up so the rows two "
-                                 "strips share are read once, PMC 1.001x; DESIGN.md §5)")
-                     if args.workload == "fir2d_u8" else "HBM",
-                     "kernel_avg_us": round(kern_avg_s * 1e6, 2), "algorithmic_bytes_per_launch": alg_bytes,
-                     "kernel_avg_us_ranks": {"max": round(max(kern_ranks) * 1e6, 2),
-                                             "min": round(min(kern_ranks) * 1e6, 2)},
-                     "timing": f"HIP events around {n_roof} back-to-back launches of the kernel after "
-                               f"{max(0, args.roofline_ramp)} untimed ones and at least {RAMP_MS:g} ms of them"
-                               if args.roofline_ramp > 0 else
-                               f"HIP events around {n_roof} back-to-back launches of the kernel, no ramp"},
-        "cpu_baseline": cpu,
-        "cpu_baseline_numpy": cpu_np,
-        "cpu_baseline_numpy_threads": cpu_np_mt,
-        "cpu_baseline_python_loop": cpu_loop,
-        "parity": parity,
         "host_issue_us_per_step": round(t_issue / args.steps * 1e6, 1),
     }
+    if args.full:  # what the legs after the timed steps measured and checked
+        traffic = pmc_traffic(wl)
+        alg_bytes = wl.alg_bytes
+        achieved = alg_bytes / kern_avg_s / 1e9
+        line.update({
+            "roofline": {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                         "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic,
+                         "kernel": "fir2d_mfma_kernel" if wl.gen2d else KERNELS[args.workload],
+                         "limiter": ("HBM (int8 MFMA Toeplitz rows, 32-row strips walking alternately down and up; "
+                                     "PMC 1.008x, DESIGN.md §5)" if wl.gen2d else
+                                     "HBM (separable packed-16 strips; alternate strips walk up so the rows two "
+                                     "strips share are read once, PMC 1.001x; DESIGN.md §5)")
+                         if args.workload == "fir2d_u8" else "HBM",
+                         "kernel_avg_us": round(kern_avg_s * 1e6, 2), "algorithmic_bytes_per_launch": alg_bytes,
+                         "kernel_avg_us_ranks": {"max": round(max(kern_ranks) * 1e6, 2),
+                                                 "min": round(min(kern_ranks) * 1e6, 2)},
+                         "timing": f"HIP events around {n_roof} back-to-back launches of the kernel after "
+                                   f"{max(0, args.roofline_ramp)} untimed ones and at least {RAMP_MS:g} ms of them"
+                                   if args.roofline_ramp > 0 else
+                                   f"HIP events around {n_roof} back-to-back launches of the kernel, no ramp"},
+            "cpu_baseline": cpu,
+            "cpu_baseline_numpy": cpu_np,
+            "cpu_baseline_numpy_threads": cpu_np_mt,
+            "cpu_baseline_python_loop": cpu_loop,
+            "parity": parity,
+        })
     if os.environ.get("FIR_BENCH_REHEARSAL"):
         line["config"] = dict(line["config"], rehearsal=(
             f"{os.environ['FIR_BENCH_REHEARSAL']}: gloo process group, ranks share the GPU's HBM; not a "
@@ -1106,7 +1182,8 @@ def main() -> int:
         line["config"] = dict(line["config"], halo=halo)
     if legs is not None:
         line["legs"] = legs
-        line["strong_scaling"] = strong
+        if args.full:
+            line["strong_scaling"] = strong
     if wl.sharded_1d and world == 1:
         line["config"] = dict(wl.config, rehearsal=f"FIR_SELF_HALO=1: {wl.halo_kind} halo hand-off with itself every "
                                                     f"step (ring of one), gate mode {GATE_MODE}")

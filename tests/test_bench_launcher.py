@@ -291,3 +291,32 @@ def test_pmc_traffic_only_for_the_running_build(tmp_path):
     assert b.pmc_traffic(wl, tmp_path) is None  # no build id: taken before round 6
     path.write_text(json.dumps(dict(base, build_id=fir_hip.build_id(), algorithmic_bytes_per_launch=5)))
     assert b.pmc_traffic(wl, tmp_path) is None  # another size
+
+
+def test_dump_outputs_is_a_fixed_exact_sample(tmp_path, monkeypatch):
+    """--dump-outputs: a small output is written whole, a large one as the same elements in every
+    run (head, seeded middle, tail) within its share of the byte budget; 8-bit outputs as float32,
+    wider ones as float64, both exact."""
+    import types
+
+    import numpy as np
+    import torch
+
+    import bench as b
+
+    monkeypatch.setattr(b, "DUMP_BUDGET", 2 * 4000)  # two outputs: 1000 float32 / 500 float64 each
+    small = torch.arange(-200, 200, dtype=torch.int32) * 10_000_001  # needs float64
+    big = (torch.arange(100_002) % 251).to(torch.uint8).reshape(-1, 7)
+    wl = types.SimpleNamespace(world=1, outputs=lambda: {"small": small, "big": big})
+    b.dump_outputs(wl, tmp_path / "a")
+    b.dump_outputs(wl, tmp_path / "b")
+    got_s, got_b = np.load(tmp_path / "a" / "small.npy"), np.load(tmp_path / "a" / "big.npy")
+    assert sorted(p.name for p in (tmp_path / "a").iterdir()) == ["big.npy", "small.npy"]
+    assert got_s.dtype == np.float64 and np.array_equal(got_s, small.numpy().astype(np.float64))
+    flat = big.reshape(-1).numpy()
+    assert got_b.dtype == np.float32 and got_b.size == 1000
+    assert np.array_equal(got_b[:250], flat[:250]) and np.array_equal(got_b[-250:], flat[-250:])
+    assert np.array_equal(got_b, np.load(tmp_path / "b" / "big.npy"))
+    # the middle is a sorted draw without repeats from what lies between the two edges
+    want = np.sort(np.random.default_rng(b.SEED).choice(flat.size - 500, 500, replace=False)) + 250
+    assert np.array_equal(got_b[250:750], flat[want])

@@ -14,7 +14,7 @@ export TMPDIR=/tmp MASTER_ADDR=127.0.0.1 MASTER_PORT=$((29600 + RANDOM % 300)) W
 pids=()
 for r in 0 1; do
     RANK=$r LOCAL_RANK=$r timeout -k 10 240 rocprofv3 --kernel-trace --stats -d "$OUT/rank$r" -o run \
-        --output-format csv -- python3 bench.py --gpus 2 --steps "$STEPS" --warmup 100 --cpu-seconds 0 \
+        --output-format csv -- python3 bench.py --full --gpus 2 --steps "$STEPS" --warmup 100 --cpu-seconds 0 \
         > "$OUT/rank$r.log" 2>&1 &
     pids+=($!)
 done

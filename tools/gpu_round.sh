@@ -33,38 +33,38 @@ for s in $STEPS; do
         smoke) run smoke 300 python -c "import __graft_entry__ as g; g.smoke()"; rc=$?; [ $rc -ne 0 ] && exit $rc ;;
         pytest) run pytest_gpu 700 python -u -m pytest tests -m gpu -q -p no:cacheprovider -x --timeout 120 --timeout-method thread; fatal $? ;;
         pytestall) run pytest_gpu 700 python -u -m pytest tests -m gpu -q -p no:cacheprovider --timeout 120 --timeout-method thread; fatal $? ;;
-        bench) run bench 300 python bench.py; fatal $? ;;
-        benchcplx) run bench_cplx 300 python bench.py --workload cplx_i16 --cpu-seconds 5; fatal $? ;;
-        bench2d) run bench_2d 300 python bench.py --workload fir2d_u8 --cpu-seconds 5; fatal $? ;;
+        bench) run bench 300 python bench.py --full; fatal $? ;;
+        benchcplx) run bench_cplx 300 python bench.py --full --workload cplx_i16 --cpu-seconds 5; fatal $? ;;
+        bench2d) run bench_2d 300 python bench.py --full --workload fir2d_u8 --cpu-seconds 5; fatal $? ;;
         prof) run prof 300 rocprofv3 --kernel-trace --stats -d "$OUT/prof" -o run --output-format csv -- \
-                  python bench.py --steps 200 --warmup 100 --cpu-seconds 0 --no-parity --no-configs; fatal $? ;;
+                  python bench.py --full --steps 200 --warmup 100 --cpu-seconds 0 --no-parity --no-configs; fatal $? ;;
         pmc) for c in FETCH_SIZE WRITE_SIZE; do
                  run "pmc_$c" 300 rocprofv3 --pmc "$c" --kernel-trace -d "$OUT/pmc_$c" -o run --output-format csv -- \
-                     python bench.py --steps 10 --warmup 2 --cpu-seconds 0 --no-parity --no-configs --roofline-launches 5 \
+                     python bench.py --full --steps 10 --warmup 2 --cpu-seconds 0 --no-parity --no-configs --roofline-launches 5 \
                      --roofline-ramp 0; fatal $? || exit
              done ;;
         bench_*) wl=${s#bench_}
-             run "bench_$wl" 300 python bench.py --workload "$wl" --cpu-seconds 5; fatal $? ;;
+             run "bench_$wl" 300 python bench.py --full --workload "$wl" --cpu-seconds 5; fatal $? ;;
         prof_*) wl=${s#prof_}
              run "prof_$wl" 300 rocprofv3 --kernel-trace --stats -d "$OUT/prof_$wl" -o run --output-format csv -- \
-                 python bench.py --workload "$wl" --steps 200 --warmup 100 --cpu-seconds 0 --no-parity; fatal $? ;;
+                 python bench.py --full --workload "$wl" --steps 200 --warmup 100 --cpu-seconds 0 --no-parity; fatal $? ;;
         pmc_*) wl=${s#pmc_}
              for c in FETCH_SIZE WRITE_SIZE; do
                  run "pmc_${wl}_$c" 300 rocprofv3 --pmc "$c" --kernel-trace -d "$OUT/pmc_${wl}_$c" -o run \
-                     --output-format csv -- python bench.py --workload "$wl" --steps 10 --warmup 2 --cpu-seconds 0 \
+                     --output-format csv -- python bench.py --full --workload "$wl" --steps 10 --warmup 2 --cpu-seconds 0 \
                      --no-parity --roofline-launches 5 --roofline-ramp 0; fatal $? || exit
              done ;;
         pytestsub) run pytest_sub 600 python -u -m pytest -x -q -p no:cacheprovider --timeout 120 \
                  --timeout-method thread ${PYTEST_FILES}; fatal $? ;;
-        benchdrv) run bench_drv 300 python bench.py --gpus 1 --steps 20 --warmup 5; fatal $? ;;
+        benchdrv) run bench_drv 300 python bench.py --full --gpus 1 --steps 20 --warmup 5; fatal $? ;;
         launch2|launch4) n=${s#launch}
-             run "launch$n" 400 python bench.py --gpus "$n" --steps 20 --warmup 5; fatal $? ;;
+             run "launch$n" 400 python bench.py --full --gpus "$n" --steps 20 --warmup 5; fatal $? ;;
         self_serial|self_overlap) m=${s#self_}
-             run "self_$m" 300 env FIR_SELF_HALO=1 FIR_HALO=xgmi FIR_GATE_MODE=$m python bench.py --cpu-seconds 0; fatal $? ;;
-        self_rccl) run self_rccl 300 env FIR_SELF_HALO=1 FIR_HALO=rccl python bench.py --cpu-seconds 0; fatal $? ;;
+             run "self_$m" 300 env FIR_SELF_HALO=1 FIR_HALO=xgmi FIR_GATE_MODE=$m python bench.py --full --cpu-seconds 0; fatal $? ;;
+        self_rccl) run self_rccl 300 env FIR_SELF_HALO=1 FIR_HALO=rccl python bench.py --full --cpu-seconds 0; fatal $? ;;
         profself_serial|profself_overlap) m=${s#profself_}
              run "profself_$m" 300 env FIR_SELF_HALO=1 FIR_HALO=xgmi FIR_GATE_MODE=$m rocprofv3 --kernel-trace --stats \
-                 -d "$OUT/profself_$m" -o run --output-format csv -- python bench.py --steps 200 --warmup 100 \
+                 -d "$OUT/profself_$m" -o run --output-format csv -- python bench.py --full --steps 200 --warmup 100 \
                  --cpu-seconds 0 --no-parity; fatal $? ;;
         metab) run metab 300 python tools/metrics_ab.py warmup-fir-filter_amd/fir_hip/libfir_hip.so abrun/libfir_hip_old.so \
                  abrun/libfir_hip_oldnoasm.so abrun/libfir_hip_glds0.so abrun/libfir_hip_glds768.so abrun/libfir_hip_glds256.so; fatal $? ;;
@@ -73,7 +73,7 @@ for s in $STEPS; do
         sq_*) wl=${s#sq_}
              run "sq_$wl" 150 rocprofv3 --pmc SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY \
                  SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_LDS_BANK_CONFLICT SQ_INSTS_VALU --kernel-trace \
-                 -d "$OUT/sq_$wl" -o run --output-format csv -- python bench.py --workload "$wl" --steps 10 \
+                 -d "$OUT/sq_$wl" -o run --output-format csv -- python bench.py --full --workload "$wl" --steps 10 \
                  --warmup 2 --cpu-seconds 0 --no-parity --roofline-launches 5 --roofline-ramp 0; fatal $? ;;
         dist2prof_serial|dist2prof_overlap) m=${s#dist2prof_}
              run "dist2prof_$m" 300 tools/dist2_prof.sh "$OUT/dist2prof_$m" "$m"; fatal $? ;;
@@ -86,7 +86,7 @@ for s in $STEPS; do
         probe) run probe 200 python tools/pipeline_probe.py; fatal $? ;;
         profwl_*) wl=${s#profwl_}
              run "profwl_$wl" 300 rocprofv3 --kernel-trace --stats -d "$OUT/profwl_$wl" -o run --output-format csv -- \
-                 python bench.py --workload "$wl" --steps 200 --warmup 100 --cpu-seconds 0 --no-parity; fatal $? ;;
+                 python bench.py --full --workload "$wl" --steps 200 --warmup 100 --cpu-seconds 0 --no-parity; fatal $? ;;
         libab_*) wl=${s#libab_}
              run "libab_$wl" 200 python tools/lib_ab.py warmup-fir-filter_amd/fir_hip/libfir_hip.so ${AB_LIB} 10 "$wl"; fatal $? ;;
         ltab_*) kind=${s#ltab_}
@@ -118,7 +118,7 @@ for s in $STEPS; do
                  abrun/libfir_hip_met_b256t4k.so --no-check; fatal $? ;;
         ktrace_*) wl=${s#ktrace_}
              run "ktrace_$wl" 150 rocprofv3 --kernel-trace -d "$OUT/ktrace_$wl" -o run --output-format csv -- \
-                 python bench.py --workload "$wl" --steps 20 --warmup 10 --cpu-seconds 0 --no-parity \
+                 python bench.py --full --workload "$wl" --steps 20 --warmup 10 --cpu-seconds 0 --no-parity \
                  --roofline-launches 20 --roofline-ramp 10; fatal $? ;;
         sqlt_*) kind=${s#sqlt_}
               run "sq_lt257_$kind" 150 rocprofv3 --pmc SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY \
@@ -151,7 +151,7 @@ for s in $STEPS; do
         microu8) run microu8 300 tools/microbench/fir_u8_micro 15; fatal $? ;;
         dist2|dist4) n=${s#dist}
              run "dist$n" 300 env FIR_DIST_BACKEND=gloo python -m torch.distributed.run --nnodes=1 \
-                 --nproc-per-node "$n" --master-addr 127.0.0.1 --master-port 29513 bench.py --gpus "$n" \
+                 --nproc-per-node "$n" --master-addr 127.0.0.1 --master-port 29513 bench.py --full --gpus "$n" \
                  --steps 5 --warmup 2 --cpu-seconds 0 --log2n 24; fatal $? ;;
         *) echo "unknown step $s"; exit 2 ;;
     esac

@@ -41,7 +41,7 @@ def main() -> None:
                "traffic_over_algorithmic": round((rd + wr) / alg, 4),
                "correction": "FETCH_SIZE x2 (gfx950 reports half of wide coalesced streaming reads), WRITE_SIZE x1",
                "per": f"call (all dispatches matching {kernels!r} / dispatches of {marker!r})",
-               "source": f"rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE --kernel-trace, separate passes, python bench.py "
+               "source": f"rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE --kernel-trace, separate passes, python bench.py --full "
                          f"--workload {wl} --steps 10 --warmup 2 (tools/gpu_round.sh pmc_{wl})"}
     out.write_text(json.dumps(summary, indent=1) + "\n")
     print(json.dumps(summary, indent=1))

@@ -23,7 +23,7 @@ for wl in $WLS; do
     for c in FETCH_SIZE WRITE_SIZE; do
         echo "== $wl $c"
         timeout -s KILL 120 rocprofv3 --pmc "$c" --kernel-trace -d "$OUT/pmc_${wl}_$c" -o run --output-format csv -- \
-            python bench.py --workload "$wl" --steps 10 --warmup 2 --cpu-seconds 0 --no-parity \
+            python bench.py --full --workload "$wl" --steps 10 --warmup 2 --cpu-seconds 0 --no-parity \
             --roofline-launches 5 --roofline-ramp 0 > "$OUT/pmc_${wl}_$c.log" 2>&1 || { echo "pass failed"; exit 1; }
     done
     python tools/pmc_summary.py "$OUT" "${KERN[$wl]}" "${ALG[$wl]}" "$OUT/pmc_$wl.json" "pmc_${wl}_" || exit 1
