@@ -1,6 +1,10 @@
 """Property-based GPU parity (hypothesis, derandomized): random shapes, tap sets, bit widths,
-channel counts, buffer alignments and halos through the C ABI, each compared bit-exactly with
+channel counts, misaligned host arrays and halos through the C ABI, each compared bit-exactly with
 the C oracle (itself pinned to the reference's golden vectors by tests/test_oracle_golden.py).
+The misalignment is the host array's only: the host entries stage every call in 16-byte aligned
+device scratch, so the kernels and the dispatchers' pointer-alignment branches see aligned
+pointers here; misaligned device pointers, and guard bands around every device buffer, are
+tests/test_gpu_containment.py's.
 
 Complements the fixed parameter grids of test_gpu_fir1d.py / test_gpu_fir2d_ideal.py: the
 strategies cover every kernel the launchers can pick (register v_dot2 / byte-pair / packed-16 /
