@@ -33,6 +33,9 @@
  *                         §8(e)); no reference counterpart (the reference is one process).
  *   fir2d_fixed[_dev]     fir_2d/model/cpp/CMakeLists.txt is empty in the reference; the
  *                         2-D semantics are the build's.
+ *   fir2d_ideal[_frames][_dev] none: the reference has no 2-D model at all; the semantics are
+ *                         the build's (the contract above the entries), the 2-D extension of
+ *                         fir_1d_ideal with fir2d_fixed's centre rule.
  *   fir1d_ideal_rows[_dev] fir_1d/model/python/fir_1d_ref.py:43-65 (fir_1d_ideal) per row as
  *                         in fir_1d/sim/vector/gen_ideal_output.py:37-50.
  *   fir_compare_metrics   fir_1d/sim/vector/gen_3tap_compare_report.py:67-112 (_compute_metrics).
@@ -214,6 +217,37 @@ int fir1d_ideal_rows(const uint8_t* x, int64_t rows, int64_t width, const double
                      double* y, int device);
 int fir1d_ideal_rows_dev(const uint8_t* x_dev, int64_t rows, int64_t width, const double* h,
                          int taps, double* y_dev, void* stream);
+
+/* ---- float64 "ideal" model of the 2-D FIR --------------------------------------------
+ * The ideal side of the 2-D fixed-vs-ideal check (the assignment's fir_2d "float sum"; rounding
+ * and the [0,255] clip are the caller's: fir_restore_u8).  Arithmetic contract:
+ *
+ *   y[i,j] = acc after:  acc = +0.0
+ *                        for m in 0..tap_rows-1:          (outer, ascending)
+ *                          for n in 0..tap_cols-1:        (inner, ascending)
+ *                            acc = acc + h[m*tap_cols+n] * x[i - m + tap_rows/2][j - n + tap_cols/2]
+ *
+ * x uint8 (height x width), h float64 (host memory, row-major), y float64 of x's shape.  Every
+ * product and every sum is rounded on its own (round to nearest even, never fused); samples
+ * outside the frame are zero; no output clamp.  It is the 2-D extension of fir1d_ideal_rows with
+ * the centre rule of fir2d_fixed.  Part of the contract, and tested: the ORDER of the additions
+ * (m outer, n inner, both ascending -- another order changes the bytes of most outputs); the
+ * accumulator starts at +0.0 (a zero frame gives +0.0 under any taps, never -0.0); no matrix-core
+ * (fused) accumulation.  Frames of a batch are independent.  Non-finite h is for the host layer
+ * to reject; these entries do not define it.  Conventions of fir2d_fixed*: frames <= 65535, empty
+ * problems are no-ops returning FIR_OK, the _dev forms enqueue on the caller's stream and never
+ * synchronise (nor allocate when tap_rows, tap_cols <= 5, width % 4 == 0, x 4-byte and y 16-byte
+ * aligned: the register kernel; every other call reads its taps from a cached device table, whose
+ * first use cannot be captured in a hipGraph).  Added without an ABI number change (additive; the
+ * build id already refuses a stale library). */
+int fir2d_ideal(const uint8_t* x, int64_t height, int64_t width, const double* h, int tap_rows,
+                int tap_cols, double* y, int device);
+int fir2d_ideal_dev(const uint8_t* x_dev, int64_t height, int64_t width, const double* h,
+                    int tap_rows, int tap_cols, double* y_dev, void* stream);
+int fir2d_ideal_frames(const uint8_t* x, int64_t frames, int64_t height, int64_t width, const double* h,
+                       int tap_rows, int tap_cols, double* y, int device);
+int fir2d_ideal_frames_dev(const uint8_t* x_dev, int64_t frames, int64_t height, int64_t width,
+                           const double* h, int tap_rows, int tap_cols, double* y_dev, void* stream);
 
 /* ---- fixed-vs-ideal comparison metrics -----------------------------
  * One pass over `n` samples of ideal (float64) and fixed outputs of `fixed_dtype` (the

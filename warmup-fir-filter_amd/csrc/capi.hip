@@ -816,6 +816,47 @@ int fir1d_ideal_rows_dev(const uint8_t* x_dev, int64_t rows, int64_t width, cons
     }
 }
 
+int fir2d_ideal_frames(const uint8_t* x, int64_t frames, int64_t height, int64_t width, const double* h, int tap_rows,
+                       int tap_cols, double* y, int device) {
+    try {
+        std::string err;
+        if (const int rc = fir::check_fir2d_ideal(frames, height, width, h, tap_rows, tap_cols, &err)) return fail(rc, err);
+        int64_t n = 0, hw = 0;
+        if (!mul_ok(height, width, &hw) || !mul_ok(hw, frames, &n) || n > INT64_MAX / 8)
+            return fail(FIR_EINVAL, "invalid frames/height/width");
+        if (n == 0) return FIR_OK;
+        if (!x || !y) return fail(FIR_EINVAL, "x and y must not be NULL");
+        return run_host(device, x, (size_t)n, y, (size_t)n * 8, [&](void* dx, void* dy, hipStream_t s, std::string* e) {
+            return fir::launch_fir2d_ideal((const uint8_t*)dx, frames, height, width, h, tap_rows, tap_cols, (double*)dy,
+                                           s, e);
+        });
+    } catch (...) {
+        return fail(FIR_EHIP, "internal error");
+    }
+}
+
+int fir2d_ideal(const uint8_t* x, int64_t height, int64_t width, const double* h, int tap_rows, int tap_cols, double* y,
+                int device) {
+    return fir2d_ideal_frames(x, 1, height, width, h, tap_rows, tap_cols, y, device);
+}
+
+int fir2d_ideal_frames_dev(const uint8_t* x_dev, int64_t frames, int64_t height, int64_t width, const double* h,
+                           int tap_rows, int tap_cols, double* y_dev, void* stream) {
+    try {
+        std::string err;
+        int rc = fir::launch_fir2d_ideal(x_dev, frames, height, width, h, tap_rows, tap_cols, y_dev, (hipStream_t)stream,
+                                         &err);
+        return rc ? fail(rc, err) : FIR_OK;
+    } catch (...) {
+        return fail(FIR_EHIP, "internal error");
+    }
+}
+
+int fir2d_ideal_dev(const uint8_t* x_dev, int64_t height, int64_t width, const double* h, int tap_rows, int tap_cols,
+                    double* y_dev, void* stream) {
+    return fir2d_ideal_frames_dev(x_dev, 1, height, width, h, tap_rows, tap_cols, y_dev, stream);
+}
+
 int fir1d_ideal_images_multi(int n_images, const uint8_t* const* xs, const int64_t* rows, const int64_t* widths,
                              const double* h, int taps, int filters, double* const* y_planes, int device,
                              fir_plane_ready_fn ready, void* ready_ctx, double* timing_ms) {

@@ -101,6 +101,13 @@ int launch_fir2d(const uint8_t* x, int64_t frames, int64_t height, int64_t width
 int launch_fir1d_ideal(const uint8_t* x, int64_t rows, int64_t width, const double* h, int L, double* y,
                        hipStream_t stream, std::string* err);
 
+// float64 ideal model of the 2-D FIR over `frames` uint8 frames stored back to back (ideal2d.hip).
+// check_fir2d_ideal: the structural checks alone (what a host entry refuses before it needs a device).
+int check_fir2d_ideal(int64_t frames, int64_t height, int64_t width, const double* h, int tap_rows, int tap_cols,
+                      std::string* err);
+int launch_fir2d_ideal(const uint8_t* x, int64_t frames, int64_t height, int64_t width, const double* h, int tap_rows,
+                       int tap_cols, double* y, hipStream_t stream, std::string* err);
+
 // Fixed-vs-ideal comparison metrics (one pass); `work` >= metrics_work_bytes(n).
 size_t metrics_work_bytes(int64_t n);
 int metrics_dtype_size(int fixed_dtype);  // bytes per element of a fir_num_dtype, 0 if unknown

@@ -7,7 +7,7 @@ CPU fallback: the product path fails loudly rather than computing elsewhere.
 
 Host-array entry points (NumPy in, NumPy out, synchronous):
     fir1d_fixed_rows, fir1d_fixed_rows_multi, fir1d_fixed_rows_sharded, fir2d_fixed,
-    fir1d_ideal_rows, compare_metrics, restore_u8, and the stage drivers' image batches
+    fir2d_ideal, fir1d_ideal_rows, compare_metrics, restore_u8, and the stage drivers' image batches
     fir1d_fixed_images_multi / fir1d_ideal_images_multi (page-locked staging: host_empty)
 Device entry points (torch tensors on a HIP device, enqueued on the current stream):
     see :mod:`fir_hip.torch_ops`.
@@ -23,7 +23,7 @@ import numpy as np
 
 __all__ = [
     "FirHipError", "lib", "lib_path", "device_count", "fir1d_fixed_rows", "fir1d_fixed_rows_multi",
-    "fir1d_fixed_rows_sharded", "fir2d_fixed", "fir1d_ideal_rows", "compare_metrics", "restore_u8", "IN_U8", "IN_I16",
+    "fir1d_fixed_rows_sharded", "fir2d_fixed", "fir2d_ideal", "fir1d_ideal_rows", "compare_metrics", "restore_u8", "IN_U8", "IN_I16",
     "OUT_U8_SAT", "OUT_I32", "RESTORE_CLIP", "RESTORE_NORMALIZE", "MAX_TAPS", "EXPORTS", "ipc_export", "ipc_import",
     "ipc_close", "peek", "IPC_HANDLE_BYTES", "device_bus_id", "peer_access", "peer_atomics", "halo_mailbox_bytes",
     "GATE_TIMEOUT", "GATE_LAYOUT", "build_id", "parse_devices", "METRIC_DTYPES", "fir1d_fixed_images_multi",
@@ -75,6 +75,10 @@ EXPORTS = {
     "fir2d_fixed_dev": (_i32, [_vp, _i64, _i64, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
     "fir2d_fixed_frames": (_i32, [_vp, _i64, _i64, _i64, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _i32]),
     "fir2d_fixed_frames_dev": (_i32, [_vp, _i64, _i64, _i64, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
+    "fir2d_ideal": (_i32, [_vp, _i64, _i64, _vp, _i32, _i32, _vp, _i32]),
+    "fir2d_ideal_dev": (_i32, [_vp, _i64, _i64, _vp, _i32, _i32, _vp, _vp]),
+    "fir2d_ideal_frames": (_i32, [_vp, _i64, _i64, _i64, _vp, _i32, _i32, _vp, _i32]),
+    "fir2d_ideal_frames_dev": (_i32, [_vp, _i64, _i64, _i64, _vp, _i32, _i32, _vp, _vp]),
     "fir1d_ideal_rows": (_i32, [_vp, _i64, _i64, _vp, _i32, _vp, _i32]),
     "fir1d_ideal_rows_dev": (_i32, [_vp, _i64, _i64, _vp, _i32, _vp, _vp]),
     "fir_metrics_work_bytes": (_i64, [_i64]),
@@ -570,6 +574,33 @@ def fir2d_fixed(x: np.ndarray, hq2, frac_bits: int = 12, acc_bits: int = 32, out
     frames = x.shape[0] if x.ndim == 3 else 1
     _check(lib().fir2d_fixed_frames(_ptr(x), frames, x.shape[-2], x.shape[-1], _ptr(h), R, C, int(frac_bits),
                                     int(acc_bits), int(out_stage), _ptr(y), int(device)), "fir2d_fixed_frames")
+    return y
+
+
+def _taps2_f64(h2) -> np.ndarray:
+    """A (R, C) float64 kernel, C-contiguous; refused before any library call otherwise."""
+    h = np.asarray(h2, dtype=np.float64)
+    if h.ndim != 2 or h.size == 0:
+        raise FirHipError("h2 must be a non-empty 2-D array")
+    if h.size > MAX_TAPS:
+        raise FirHipError(f"{h.size} taps exceed the library limit of {MAX_TAPS}")
+    return np.ascontiguousarray(h)
+
+
+def fir2d_ideal(x: np.ndarray, h2, device: int = 0, out: np.ndarray | None = None) -> np.ndarray:
+    """float64 ideal model of the 2-D FIR: a uint8 frame (H, W), or a batch of frames (F, H, W)
+    each filtered on its own in one launch, with a (R, C) float64 kernel.  Returns float64 of
+    x's shape: the sum over m, then n (both ascending) of h2[m, n] * x[i - m + R//2, j - n + C//2],
+    every product and sum rounded on its own, zero outside the frame, no clamp."""
+    x = np.ascontiguousarray(x, dtype=np.uint8)
+    if x.ndim not in (2, 3):
+        raise FirHipError("x must be 2-D (a frame) or 3-D (frames, height, width)")
+    h = _taps2_f64(h2)
+    R, C = h.shape
+    y = _out_buf(out, x.shape, np.float64, x)
+    frames = x.shape[0] if x.ndim == 3 else 1
+    _check(lib().fir2d_ideal_frames(_ptr(x), frames, x.shape[-2], x.shape[-1], _ptr(h), R, C, _ptr(y), int(device)),
+           "fir2d_ideal_frames")
     return y
 
 

@@ -11,8 +11,8 @@ import ctypes
 import numpy as np
 import torch
 
-from . import (IN_I16, IN_U8, OUT_I32, OUT_U8_SAT, RESTORE_CLIP, RESTORE_NORMALIZE, FirHipError, _check, _taps_i32,
-               lib)
+from . import (IN_I16, IN_U8, OUT_I32, OUT_U8_SAT, RESTORE_CLIP, RESTORE_NORMALIZE, FirHipError, _check, _taps2_f64,
+               _taps_i32, lib)
 
 _IN = {torch.uint8: IN_U8, torch.int16: IN_I16}
 _OUT_DTYPE = {OUT_U8_SAT: torch.uint8, OUT_I32: torch.int32}
@@ -271,6 +271,26 @@ def fir2d_fixed_dev(x: torch.Tensor, hq2, frac_bits: int = 12, acc_bits: int = 3
     _check(lib().fir2d_fixed_frames_dev(ctypes.c_void_p(x.data_ptr()), frames, x.shape[-2], x.shape[-1], t.ptr, R, C,
                                         int(frac_bits), int(acc_bits), int(out_stage), ctypes.c_void_p(out.data_ptr()),
                                         _stream_ptr(x, stream)), "fir2d_fixed_frames_dev")
+    return out
+
+
+def fir2d_ideal_dev(x: torch.Tensor, h2, out: torch.Tensor | None = None, stream=None) -> torch.Tensor:
+    """float64 ideal model of the 2-D FIR of a uint8 device frame (H, W) or batch of frames
+    (F, H, W), one launch; the twin of fir2d_fixed_dev (see fir_hip.fir2d_ideal)."""
+    _check_dev(x, "x")
+    if x.dtype != torch.uint8 or x.dim() not in (2, 3):
+        raise FirHipError("x must be a 2-D (frame) or 3-D (frames, height, width) uint8 device tensor")
+    h = _taps2_f64(h2)
+    R, C = h.shape
+    if out is None:
+        out = torch.empty(x.shape, dtype=torch.float64, device=x.device)
+    _check_dev(out, "out")
+    if out.shape != x.shape or out.dtype != torch.float64:
+        raise FirHipError("out must be float64 of x's shape")
+    frames = x.shape[0] if x.dim() == 3 else 1
+    _check(lib().fir2d_ideal_frames_dev(ctypes.c_void_p(x.data_ptr()), frames, x.shape[-2], x.shape[-1],
+                                        h.ctypes.data_as(ctypes.c_void_p), R, C, ctypes.c_void_p(out.data_ptr()),
+                                        _stream_ptr(x, stream)), "fir2d_ideal_frames_dev")
     return out
 
 
