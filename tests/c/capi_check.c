@@ -52,6 +52,10 @@ int main(void) {
         expect(fir_peer_access(0, NULL, &can) == FIR_EINVAL, "peer access null");
         expect(fir_device_bus_id(0, bus, 8) == FIR_EINVAL, "bus id short buffer");
     }
+    expect(fir_device_count(NULL) == FIR_EINVAL, "device count null");
+    expect(fir_host_free(NULL) == FIR_OK, "host free null, no device");
+    expect(fir_halo_mailbox_bytes(-1, 0) == -1 && fir_halo_mailbox_bytes(0, -1) == -1, "mailbox bytes negative");
+    expect(fir_halo_mailbox_bytes(0, 0) > 0 && fir_halo_mailbox_bytes(16, 16) % 4 == 0, "mailbox bytes");
     expect(strlen(fir_last_error()) > 0, "error text");
     if (!have) {
         uint8_t x[64] = {0}, y[64];

@@ -126,6 +126,329 @@ def test_ipc_argument_checks_without_device(lib):
     assert lib.fir_peer_access(0, b"0000:00:00.0", None) == 1
 
 
+def _refusal_table(chunked_on: bool):
+    """(entry, arguments, status, substring of fir_last_error) for calls that are settled before a
+    device is needed, or (device index _NO_DEV) at the device lookup.  The rows pin the ORDER of
+    the checks inside each entry as well as their texts: a call that is wrong in two ways names
+    the check that comes first."""
+    h = (ctypes.c_int32 * 6)(1, 2, 1, -1, 0, 1)
+    hd = (ctypes.c_double * 6)(0.25, 0.5, 0.25, -1.0, 0.0, 1.0)
+    buf = np.zeros(1024, np.uint8)  # real memory behind every non-NULL data pointer
+    X = Y = buf.ctypes.data
+    i64x2, vpx2 = ctypes.c_int64 * 2, ctypes.c_void_p * 2
+    xs, ys, ys4 = vpx2(X, X), vpx2(Y, Y), (ctypes.c_void_p * 4)(Y, Y, Y, Y)
+    r2, w2, zero2 = i64x2(2, 2), i64x2(16, 16), i64x2(0, 0)
+    devs = (ctypes.c_int32 * 1)(_NO_DEV)
+    BIG = 1 << 62
+    EINVAL, ENODEV = 1, 3
+    t = []
+
+    def rows_like(fn, tail, multi=False):
+        """The five entries that share (x, in_dtype, rows, width, channels, hq, taps[, filters],
+        frac_bits, acc_bits, out_stage, y): fn(**overrides) -> argument tuple."""
+        def args(x=None, in_dtype=0, rows=0, width=16, ch=1, hq=h, taps=3, filters=2, frac=12, acc=32, stage=0,
+                 y=None):
+            f = (filters,) if multi else ()
+            return (x, in_dtype, rows, width, ch, hq, taps) + f + (frac, acc, stage, y) + tail
+        return lambda rc, msg, **kw: t.append((fn, args(**kw), rc, msg))
+
+    for fn, multi in (("fir1d_fixed_rows_dev", False), ("fir1d_fixed_rows_multi_dev", True)):
+        add = rows_like(fn, (None,), multi)
+        add(0, b"")
+        add(EINVAL, b"in_dtype must be FIR_IN_U8 or FIR_IN_I16", in_dtype=7)
+        add(EINVAL, b"in_dtype must be", in_dtype=7, stage=5, taps=0)
+        add(EINVAL, b"out_stage must be FIR_OUT_U8_SAT or FIR_OUT_I32", stage=5, rows=-1)
+        add(EINVAL, b"rows and width must be >= 0", rows=-1, ch=0)
+        add(EINVAL, b"channels must be >= 1", ch=0, hq=None)
+        add(EINVAL, b"hq must not be NULL", hq=None, taps=0)
+        add(EINVAL, b"taps must be in [1, ", taps=0, frac=0)
+        add(EINVAL, b"frac_bits and acc_bits must be >= 1", frac=0)
+        add(EINVAL, b"frac_bits and acc_bits must be >= 1", acc=0, rows=1)
+        add(EINVAL, b"x and y must not be NULL", rows=1)
+        add(EINVAL, b"x and y must not be NULL", rows=1, x=X)
+        if multi:
+            add(EINVAL, b"filters must be >= 1", filters=0, in_dtype=7)
+
+    for fn in ("fir1d_fixed_edges_dev", "fir1d_fixed_segment_dev"):
+        def add(rc, msg, x=None, in_dtype=0, n=0, ch=1, hq=h, taps=3, frac=12, acc=32, stage=0, y=None, fn=fn):
+            t.append((fn, (x, in_dtype, n, ch, hq, taps, frac, acc, stage, None, None, y, None), rc, msg))
+        add(0, b"")
+        add(EINVAL, b"in_dtype must be", in_dtype=7, stage=5)
+        add(EINVAL, b"out_stage must be", stage=5, n=-1)
+        add(EINVAL, b"rows and width must be >= 0", n=-1, ch=0)
+        add(EINVAL, b"channels must be >= 1", ch=0, taps=0)
+        add(EINVAL, b"hq must not be NULL", hq=None)
+        add(EINVAL, b"taps must be in [1, ", taps=0, frac=0)
+        add(EINVAL, b"frac_bits and acc_bits must be >= 1", frac=0, n=16)
+        add(EINVAL, b"x and y must not be NULL", n=16)
+        add(EINVAL, b"x and y must not be NULL", n=16, y=Y)
+
+    # fir1d_fixed_images_multi_dev (the cases of test_images_batch_argument_checks_without_device stay)
+    def add(rc, msg, n=2, x=xs, rows=r2, widths=w2, in_dtype=0, ch=1, hq=h, taps=3, filters=1, frac=12, acc=32,
+            stage=0, planes=ys):
+        t.append(("fir1d_fixed_images_multi_dev",
+                  (n, x, rows, widths, in_dtype, ch, hq, taps, filters, frac, acc, stage, planes, None), rc, msg))
+    add(EINVAL, b"image 1: invalid rows/width/channels", rows=i64x2(2, BIG))
+    add(EINVAL, b"image 0: channels must be >= 1", ch=0)
+    add(EINVAL, b"image 0: out_stage must be", stage=5, taps=0)
+    add(EINVAL, b"image 0: taps must be in [1, ", taps=0)
+    add(EINVAL, b"image 0: hq must not be NULL", hq=None)
+    add(EINVAL, b"image 0: frac_bits and acc_bits must be >= 1", acc=0)
+    add(EINVAL, b"image 1: x and its output planes must not be NULL", planes=vpx2(Y, None))
+    add(EINVAL, b"image 0: x and its output planes must not be NULL", x=vpx2(None, X))
+    add(EINVAL, b"filters must be >= 1", filters=0, in_dtype=7)
+    add(EINVAL, b"image arrays must not be NULL", rows=None, filters=0)
+    add(EINVAL, b"images must be >= 0", n=-1, x=None)
+    add(0, b"", n=0, in_dtype=7)  # no images: nothing is looked at
+
+    for fn, frames in (("fir2d_fixed_frames_dev", True), ("fir2d_fixed_dev", False)):
+        def add(rc, msg, x=None, fr=1, H=0, W=16, hq=h, R=1, C=3, frac=12, acc=32, stage=0, y=None, fn=fn,
+                frames=frames):
+            t.append((fn, (x,) + ((fr,) if frames else ()) + (H, W, hq, R, C, frac, acc, stage, y, None), rc, msg))
+        add(0, b"")
+        add(EINVAL, b"out_stage must be FIR_OUT_U8_SAT or FIR_OUT_I32", stage=5, H=-1)
+        add(EINVAL, b"frames, height and width must be >= 0", H=-1, hq=None)
+        add(EINVAL, b"hq must not be NULL", hq=None, R=0)
+        add(EINVAL, b"tap_rows*tap_cols must be in [1, ", R=0, frac=0)
+        add(EINVAL, b"tap_rows*tap_cols must be in [1, ", R=1 << 16, C=1 << 16)
+        add(EINVAL, b"frac_bits and acc_bits must be >= 1", frac=0, H=4)
+        add(EINVAL, b"x and y must not be NULL", H=4)
+        if frames:
+            add(EINVAL, b"frames, height and width must be >= 0", fr=-1)
+            add(EINVAL, b"frames must be <= 65535 per call", fr=65536, hq=None)
+
+    add = lambda rc, msg, x=None, rows=0, width=16, hh=hd, taps=3, y=None: t.append(
+        ("fir1d_ideal_rows_dev", (x, rows, width, hh, taps, y, None), rc, msg))
+    add(0, b"")
+    add(EINVAL, b"rows and width must be >= 0", rows=-1, hh=None)
+    add(EINVAL, b"h must not be NULL", hh=None, taps=0)
+    add(EINVAL, b"taps must be in [1, ", taps=0, rows=1)
+    add(EINVAL, b"x and y must not be NULL", rows=1)
+
+    for fn, frames in (("fir2d_ideal_frames_dev", True), ("fir2d_ideal_dev", False)):
+        def add(rc, msg, x=None, fr=1, H=0, W=16, hh=hd, R=1, C=3, y=None, fn=fn, frames=frames):
+            t.append((fn, (x,) + ((fr,) if frames else ()) + (H, W, hh, R, C, y, None), rc, msg))
+        add(0, b"")
+        add(EINVAL, b"frames, height and width must be >= 0", W=-1, hh=None)
+        add(EINVAL, b"h must not be NULL", hh=None, R=0)
+        add(EINVAL, b"tap_rows*tap_cols must be in [1, ", C=0, H=4)
+        add(EINVAL, b"x and y must not be NULL", H=4)
+        if frames:
+            add(EINVAL, b"frames must be <= 65535 per call", fr=65536, hh=None)
+
+    t += [
+        ("fir_compare_metrics_dev", (None, None, 0, -1, None, None, None), EINVAL, b"n must be >= 0"),
+        ("fir_compare_metrics_dev", (None, None, 99, 0, None, Y, None), EINVAL, b"null pointer argument"),
+        ("fir_compare_metrics_dev", (None, None, 0, 8, Y, Y, None), EINVAL, b"null pointer argument"),
+        ("fir_compare_metrics_dev", (None, None, 99, 0, Y, Y, None), EINVAL, b"unknown fixed dtype"),
+        ("fir_restore_u8_dev", (None, -1, 7, None, None, None), EINVAL, b"n must be >= 0"),
+        ("fir_restore_u8_dev", (None, 0, 7, None, None, None), EINVAL,
+         b"policy must be FIR_RESTORE_CLIP or FIR_RESTORE_NORMALIZE"),
+        ("fir_restore_u8_dev", (None, 0, 0, None, None, None), 0, b""),
+        ("fir_restore_u8_dev", (None, 8, 0, None, None, None), EINVAL, b"a and out must not be NULL"),
+        ("fir_restore_u8_dev", (8, 8, 0, 16, None, None), EINVAL, b"a and out must be 16-byte aligned"),
+        ("fir_halo_mailbox_init_dev", (None, 0, -1, 0, None), EINVAL, b"halo byte counts must be in [0, 2^31)"),
+        ("fir_halo_mailbox_init_dev", (None, 1 << 20, 0, 0, None), EINVAL, b"mailbox must hold fir_halo_mailbox_bytes"),
+        ("fir_halo_mailbox_init_dev", (128, 0, 0, 0, None), EINVAL, b"mailbox must hold fir_halo_mailbox_bytes"),
+        ("fir_halo_mailbox_init_dev", (64, 1 << 20, 0, 0, None), EINVAL, b"mailbox must be 128-byte aligned"),
+        ("fir_halo_gate_dev", (None, 16, -1, 0, None, None, None, None, None, None, 1.0, None), EINVAL,
+         b"halo byte counts must be in [0, min(seg_bytes"),
+        ("fir_halo_gate_dev", (None, 16, 32, 0, None, None, None, None, None, None, 1.0, None), EINVAL,
+         b"halo byte counts must be in [0, min(seg_bytes"),
+        ("fir_halo_gate_dev", (None, 16, 4, 4, None, None, None, None, None, None, 1.0, None), EINVAL,
+         b"mailbox must not be NULL"),
+        ("fir_halo_gate_dev", (None, 16, 4, 4, 64, None, None, None, None, None, 1.0, None), EINVAL,
+         b"x and the halo buffers of present neighbours must not be NULL"),
+        ("fir_halo_gate_dev", (X, 16, 4, 4, 128, 256, None, None, None, None, 1.0, None), EINVAL,
+         b"x and the halo buffers of present neighbours must not be NULL"),
+        ("fir_halo_gate_dev", (X, 16, 4, 4, 64, None, None, None, None, None, 0.0, None), EINVAL,
+         b"mailboxes must be 128-byte aligned"),
+        ("fir_halo_gate_dev", (X, 16, 4, 4, 128, None, None, None, None, None, 0.0, None), EINVAL,
+         b"timeout_s must be in (0, 600]"),
+        ("fir_halo_gate_dev", (X, 16, 4, 4, 128, None, None, None, None, None, 601.0, None), EINVAL,
+         b"timeout_s must be in (0, 600]"),
+    ]
+
+    # ---- host-pointer entries ---------------------------------------------------------------
+    add = rows_like("fir1d_fixed_rows", (_NO_DEV,))
+    add(0, b"")
+    add(0, b"", width=0, rows=5)
+    add(EINVAL, b"invalid rows/width/channels", ch=0, in_dtype=7)
+    add(EINVAL, b"invalid rows/width/channels", rows=-1)
+    add(EINVAL, b"invalid rows/width/channels", rows=BIG, width=4)
+    add(EINVAL, b"invalid rows/width/channels", rows=3, width=BIG // 2, ch=3)
+    add(EINVAL, b"in_dtype must be", in_dtype=7, stage=5)
+    add(EINVAL, b"out_stage must be", stage=5, hq=None)
+    add(EINVAL, b"hq must not be NULL", hq=None)
+    add(EINVAL, b"taps must be in [1, ", taps=0)
+    add(EINVAL, b"frac_bits and acc_bits must be >= 1", acc=0)
+    add(EINVAL, b"x and y must not be NULL", rows=1, in_dtype=7)  # the pointers before the scalars
+    add(EINVAL, b"x and y must not be NULL", rows=1, x=X)
+    add(ENODEV, None, rows=1, x=X, y=Y)
+    add(ENODEV, None, rows=1, x=X, y=Y, in_dtype=7)  # the unchunked path looks the device up first
+    if chunked_on:  # ... the chunked path (>= 64 MiB of input) checks the scalars first
+        add(EINVAL, b"in_dtype must be", rows=1, width=1 << 26, x=X, y=Y, in_dtype=7)
+        add(EINVAL, b"taps must be in [1, ", rows=8, width=1 << 23, x=X, y=Y, taps=0)
+        add(ENODEV, None, rows=1, width=1 << 26, x=X, y=Y)
+
+    add = rows_like("fir1d_fixed_rows_sharded", (devs, 1))
+    add(0, b"")
+    add(EINVAL, b"invalid rows/width/channels", ch=0, in_dtype=7)
+    add(EINVAL, b"invalid rows/width/channels", rows=BIG, width=4)
+    add(EINVAL, b"in_dtype must be", in_dtype=7)
+    add(EINVAL, b"out_stage must be", rows=1, stage=5)  # the scalars before the pointers
+    add(EINVAL, b"taps must be in [1, ", rows=1, x=X, y=Y, taps=0)
+    add(EINVAL, b"x and y must not be NULL", rows=1, y=Y)
+    add(ENODEV, None, rows=1, x=X, y=Y)
+    add(ENODEV, None, rows=4, x=X, y=Y)
+    t.append(("fir1d_fixed_rows_sharded", (X, 0, 1, 16, 1, h, 3, 12, 32, 0, Y, devs, 0), EINVAL,
+              b"devices must list ndev >= 1 device ids"))
+    t.append(("fir1d_fixed_rows_sharded", (X, 7, 1, 16, 0, h, 3, 12, 32, 0, Y, None, 1), EINVAL,
+              b"devices must list ndev >= 1 device ids"))
+
+    add = rows_like("fir1d_fixed_rows_multi", (_NO_DEV,), multi=True)
+    add(0, b"")
+    add(EINVAL, b"invalid rows/width/channels/filters", filters=0, in_dtype=7)
+    add(EINVAL, b"invalid rows/width/channels/filters", ch=0)
+    add(EINVAL, b"invalid rows/width/channels/filters", rows=BIG, width=4)
+    add(EINVAL, b"invalid rows/width/channels/filters", rows=1, width=BIG, filters=2)
+    add(EINVAL, b"in_dtype must be", in_dtype=7, taps=0)
+    add(EINVAL, b"taps must be in [1, ", taps=0)
+    add(EINVAL, b"x and y must not be NULL", rows=1, stage=5)
+    add(ENODEV, None, rows=1, x=X, y=Y)
+    add(ENODEV, None, rows=1, x=X, y=Y, stage=5)
+
+    def add(rc, msg, n=2, x=xs, rows=r2, widths=w2, in_dtype=0, ch=1, hq=h, taps=3, filters=2, frac=12, acc=32,
+            stage=0, planes=ys4):
+        t.append(("fir1d_fixed_images_multi", (n, x, rows, widths, in_dtype, ch, hq, taps, filters, frac, acc, stage,
+                                               planes, _NO_DEV, None, None, None), rc, msg))
+    add(EINVAL, b"channels must be >= 1", ch=0, n=-1)
+    add(EINVAL, b"images must be >= 0", n=-1, filters=0)
+    add(EINVAL, b"filters must be >= 1", filters=0, x=None)
+    add(EINVAL, b"image arrays must not be NULL", widths=None)
+    add(EINVAL, b"image 1: invalid rows/width/channels", rows=i64x2(2, BIG), in_dtype=7)
+    add(EINVAL, b"image 0: invalid rows/width/channels", widths=i64x2(-1, 16))
+    add(EINVAL, b"image 1: x and its output planes must not be NULL", planes=(ctypes.c_void_p * 4)(Y, Y, Y, None))
+    add(EINVAL, b"in_dtype must be", in_dtype=7)
+    add(EINVAL, b"taps must be in [1, ", taps=0)
+    add(EINVAL, b"out_stage must be", n=0, stage=5)  # the scalars are checked for an empty batch too
+    add(0, b"", n=0, x=None, rows=None, widths=None, planes=None)
+    add(0, b"", rows=zero2, x=vpx2(None, None))
+    add(ENODEV, None)
+
+    for fn, frames in (("fir2d_fixed_frames", True), ("fir2d_fixed", False)):
+        def add(rc, msg, x=None, fr=1, H=0, W=16, hq=h, R=1, C=3, frac=12, acc=32, stage=0, y=None, fn=fn,
+                frames=frames):
+            t.append((fn, (x,) + ((fr,) if frames else ()) + (H, W, hq, R, C, frac, acc, stage, y, _NO_DEV), rc, msg))
+        add(0, b"")
+        add(EINVAL, b"invalid frames/height/width", H=-1, stage=5)
+        add(EINVAL, b"invalid frames/height/width", H=BIG, W=4)
+        add(EINVAL, b"out_stage must be", stage=5, hq=None)
+        add(EINVAL, b"hq must not be NULL", hq=None, R=0)
+        add(EINVAL, b"tap_rows*tap_cols must be in [1, ", R=0)
+        add(EINVAL, b"frac_bits and acc_bits must be >= 1", frac=0)
+        add(EINVAL, b"x and y must not be NULL", H=4, stage=5)
+        add(ENODEV, None, H=4, x=X, y=Y)
+        add(ENODEV, None, H=4, x=X, y=Y, R=0)
+        if frames:
+            add(EINVAL, b"invalid frames/height/width", fr=-1)
+            add(0, b"", fr=70000)  # an empty problem: only the taps and the stage are looked at
+
+    add = lambda rc, msg, x=None, rows=0, width=16, hh=hd, taps=3, y=None: t.append(
+        ("fir1d_ideal_rows", (x, rows, width, hh, taps, y, _NO_DEV), rc, msg))
+    add(0, b"")
+    add(EINVAL, b"invalid rows/width", rows=-1, taps=0)
+    add(EINVAL, b"invalid rows/width", rows=BIG, width=4)
+    add(EINVAL, b"h must not be NULL", hh=None, taps=0)
+    add(EINVAL, b"taps must be in [1, ", taps=0)
+    add(EINVAL, b"x and y must not be NULL", rows=1, taps=0)
+    add(ENODEV, None, rows=1, x=X, y=Y)
+    add(ENODEV, None, rows=1, x=X, y=Y, taps=0)
+
+    for fn, frames in (("fir2d_ideal_frames", True), ("fir2d_ideal", False)):
+        def add(rc, msg, x=None, fr=1, H=0, W=16, hh=hd, R=1, C=3, y=None, fn=fn, frames=frames):
+            t.append((fn, (x,) + ((fr,) if frames else ()) + (H, W, hh, R, C, y, _NO_DEV), rc, msg))
+        add(0, b"")
+        add(EINVAL, b"frames, height and width must be >= 0", H=-1, hh=None)
+        add(EINVAL, b"h must not be NULL", hh=None, R=0)
+        add(EINVAL, b"tap_rows*tap_cols must be in [1, ", R=0, H=4, x=X, y=Y)  # before the device lookup
+        add(EINVAL, b"invalid frames/height/width", H=1 << 40, W=1 << 40, x=X, y=Y)
+        add(EINVAL, b"invalid frames/height/width", H=1 << 30, W=1 << 30, x=X, y=Y)  # n * 8 overflows
+        add(EINVAL, b"x and y must not be NULL", H=4, x=X)
+        add(ENODEV, None, H=4, x=X, y=Y)
+        if frames:
+            add(EINVAL, b"frames must be <= 65535 per call", fr=65536, R=0, x=X, y=Y)
+
+    def add(rc, msg, n=2, x=xs, rows=r2, widths=w2, hh=hd, taps=3, filters=2, planes=ys4):
+        t.append(("fir1d_ideal_images_multi", (n, x, rows, widths, hh, taps, filters, planes, _NO_DEV, None, None,
+                                               None), rc, msg))
+    add(EINVAL, b"images must be >= 0", n=-1, filters=0)
+    add(EINVAL, b"filters must be >= 1", filters=0, taps=0)
+    add(EINVAL, b"image arrays must not be NULL", planes=None, taps=0)
+    add(EINVAL, b"image 1: invalid rows/width/channels", rows=i64x2(2, BIG), taps=0)
+    add(EINVAL, b"image 0: x and its output planes must not be NULL", x=vpx2(None, X))
+    add(EINVAL, b"filter 0: taps must be in [1, ", taps=0)
+    add(EINVAL, b"filter 0: h must not be NULL", hh=None)
+    # Every filter shares `taps` and h's NULL-ness, so the only second tap set that is refused where
+    # the first is not is the one whose address h + 1 * taps comes out as NULL (nothing is read).
+    add(EINVAL, b"filter 1: h must not be NULL", rows=zero2, taps=1, hh=ctypes.c_void_p(2**64 - 8))
+    add(0, b"", n=0, x=None, rows=None, widths=None, planes=None)
+    add(0, b"", rows=zero2)
+    add(ENODEV, None)
+
+    t += [
+        ("fir_compare_metrics", (X, X, 0, -1, Y, _NO_DEV), EINVAL, b"invalid arguments"),
+        ("fir_compare_metrics", (X, X, 99, 8, None, _NO_DEV), EINVAL, b"invalid arguments"),
+        ("fir_compare_metrics", (None, X, 0, 8, Y, _NO_DEV), EINVAL, b"invalid arguments"),
+        ("fir_compare_metrics", (X, X, 99, 8, Y, _NO_DEV), EINVAL, b"unknown fixed dtype"),
+        ("fir_compare_metrics", (X, X, 0, 8, Y, _NO_DEV), ENODEV, None),
+        ("fir_compare_metrics", (None, None, 0, 0, Y, _NO_DEV), ENODEV, None),  # an empty one still runs
+        ("fir_restore_u8", (X, -1, 7, Y, _NO_DEV), EINVAL, b"invalid arguments"),
+        ("fir_restore_u8", (X, 8, 7, None, _NO_DEV), EINVAL, b"invalid arguments"),
+        ("fir_restore_u8", (None, 0, 7, None, _NO_DEV), EINVAL, b"policy must be FIR_RESTORE_CLIP"),
+        ("fir_restore_u8", (None, 0, 1, None, _NO_DEV), 0, b""),
+        ("fir_restore_u8", (X, 8, 1, Y, _NO_DEV), ENODEV, None),
+        ("fir_restore_u8", (X, 8, 7, Y, _NO_DEV), ENODEV, None),
+        ("fir_host_alloc", (-1, ctypes.pointer(ctypes.c_void_p())), EINVAL, b"invalid arguments"),
+        ("fir_host_alloc", (8, None), EINVAL, b"invalid arguments"),
+        ("fir_host_alloc", (0, ctypes.pointer(ctypes.c_void_p())), 0, b""),
+        ("fir_host_free", (None,), 0, b""),
+        ("fir_device_count", (None,), EINVAL, b"count must not be NULL"),
+        ("fir_peer_atomics", (0, None, ctypes.pointer(ctypes.c_int32())), EINVAL, b"NULL argument"),
+        ("fir_peer_atomics", (0, b"0000:00:00.0", None), EINVAL, b"NULL argument"),
+        ("fir_ipc_import", (None, 0, 0, ctypes.pointer(ctypes.c_void_p())), EINVAL, b"invalid argument"),
+        ("fir_peek", (None, None, -1), EINVAL, b"invalid argument"),
+    ]
+    return t, buf
+
+
+_NO_DEV = 1 << 20  # a device index no machine has: the device lookup itself refuses it
+
+
+def test_every_entry_refuses_bad_calls_in_a_fixed_order(lib):
+    """One table over every exported entry that takes scalar arguments: the exact status and a
+    piece of the message of calls that are refused (or, empty, accepted) before a device is needed,
+    and FIR_ENODEV from the device lookup for calls that get that far: a call whose scalars are
+    wrong still ends there in the entries that look the device up first."""
+    import os
+
+    count = ctypes.c_int32(-1)
+    have = lib.fir_device_count(ctypes.byref(count)) == 0 and count.value > 0
+    nodev = b"out of range" if have else b"no HIP device available"
+    table, keep = _refusal_table(os.environ.get("FIR_HOST_CHUNKED", "1")[:1] != "0")
+    assert {fn for fn, *_ in table} >= {n for n in fir_hip.EXPORTS if n.startswith(("fir1d_", "fir2d_"))}
+    bad = []
+    for fn, args, want, msg in table:
+        rc = getattr(lib, fn)(*args)
+        err = lib.fir_last_error()
+        if rc != want or (want and (nodev if msg is None else msg) not in err):
+            bad.append((fn, args, want, msg, rc, err))
+    assert not bad, "\n".join(f"{fn}{args}: want {want} {msg!r}, got {rc} {err!r}" for fn, args, want, msg, rc, err in bad)
+    assert lib.fir_halo_mailbox_bytes(-1, 0) == -1 and lib.fir_halo_mailbox_bytes(0, -1) == -1
+    assert lib.fir_halo_mailbox_bytes(0, 0) > 0 and lib.fir_halo_mailbox_bytes(0, 0) % 4 == 0
+    del keep
+
+
 def test_out_argument_is_checked_before_any_call():
     """``out=`` (reused host output): wrong dtype/shape/layout or an overlap with
     the input is refused in the host layer, before the library is called."""

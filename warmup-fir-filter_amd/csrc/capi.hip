@@ -5,7 +5,10 @@
 // calls are reentrant across devices and serialised per device).  They are synchronous:
 // H2D copy, kernel, D2H copy, stream synchronise.  Device-pointer entries (_dev) only
 // enqueue on the caller's stream and never allocate or synchronise, so they can be
-// captured in a hipGraph.  No C++ exception crosses the boundary.
+// captured in a hipGraph.  No C++ exception crosses the boundary: every entry that can allocate
+// or calls into fir:: runs inside guarded().  A host entry takes the device through one
+// DeviceSession, and refuses what it can before that through the launchers' own check_*
+// functions (fir_launch.h).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -33,6 +36,43 @@ int fail(int code, const std::string& msg) {
     return code;
 }
 
+// The one exception guard of the boundary.
+template <typename Fn>
+int guarded(Fn fn) {
+    try {
+        return fn();
+    } catch (const std::exception& ex) {
+        return fail(FIR_EHIP, std::string("internal error: ") + ex.what());
+    } catch (...) {
+        return fail(FIR_EHIP, "internal error");
+    }
+}
+
+// fn(args..., &err) -- a fir:: check or launcher -- with its message kept for fir_last_error()
+template <typename Fn, typename... Args>
+int checked(Fn fn, Args... args) {
+    std::string err;
+    const int rc = fn(args..., &err);
+    return rc ? fail(rc, err) : FIR_OK;
+}
+
+// The body of a device-pointer entry: one launcher call.
+template <typename Fn, typename... Args>
+int dev_entry(Fn fn, Args... args) {
+    return guarded([&] { return checked(fn, args...); });
+}
+
+// A size query (-1 if it throws)
+template <typename Fn>
+int64_t guarded_size(Fn fn) {
+    int64_t v = -1;
+    (void)guarded([&] {
+        v = (int64_t)fn();
+        return (int)FIR_OK;
+    });
+    return v;
+}
+
 #define HIP_TRY(expr)                                                                          \
     do {                                                                                       \
         hipError_t _e = (expr);                                                                \
@@ -44,12 +84,13 @@ struct DeviceBuf {
     size_t cap = 0;
 };
 
+constexpr int kChunks = 8;  // pieces of a chunked host call (run_host_chunked)
+
 struct DeviceState {
     std::mutex mu;
     bool init = false;
     hipStream_t stream = nullptr;
     hipStream_t stream_d2h = nullptr;  // the chunked host path's device-to-host copies
-    static constexpr int kChunks = 8;
     hipEvent_t chunk_ev[kChunks] = {};  // the chunked host path's per-chunk kernel events
     DeviceBuf in, out;
     void* pin_in = nullptr;   // small calls: pinned host staging the kernel reads / writes directly
@@ -126,8 +167,30 @@ int init_locked(DeviceState* st, int device) {
     return FIR_OK;
 }
 
-size_t in_size(int in_dtype) { return in_dtype == FIR_IN_I16 ? 2 : 1; }
-size_t out_size(int stage) { return stage == FIR_OUT_I32 ? 4 : 1; }
+// A host entry's hold on `device`: the calling thread's current device put back at scope exit,
+// the device's state locked and initialised.  Usable only when rc == FIR_OK.
+struct DeviceSession {
+    DeviceRestore restore;
+    DeviceState* st = nullptr;
+    std::unique_lock<std::mutex> lk;
+    int rc;
+    explicit DeviceSession(int device) : rc(device_state(device, &st)) {
+        if (rc) return;
+        lk = std::unique_lock<std::mutex>(st->mu);
+        rc = init_locked(st, device);
+    }
+    // An error return after work was queued: every copy and kernel already on the stream must
+    // finish first, since the caller may free its buffers and the next call reuses the device's.
+    int drain_and_fail(int code, const std::string& msg) const {
+        (void)hipStreamSynchronize(st->stream);
+        return fail(code, msg);
+    }
+};
+
+using fir::in_size;
+using fir::out_size;
+
+size_t align256(size_t v) { return (v + 255) / 256 * 256; }
 
 // Small calls (the reference's callers run the model once per image row: 4.5 KB) skip both DMA
 // copies: the input is memcpy'd into pinned host memory, the kernel reads it and writes its
@@ -168,23 +231,17 @@ int ensure_pinned(DeviceState* st, size_t bytes) {
 template <typename F>
 int run_host(int device, const void* x, size_t in_bytes, void* y, size_t out_bytes, F launch, size_t out_skip = 0,
              size_t in_cap = 0, size_t out_cap = 0, bool small_ok = false) {
-    DeviceRestore restore;
-    DeviceState* st = nullptr;
-    int rc = device_state(device, &st);
+    DeviceSession ds(device);
+    int rc = ds.rc;
     if (rc) return rc;
-    std::lock_guard<std::mutex> lk(st->mu);
-    rc = init_locked(st, device);
-    if (rc) return rc;
+    DeviceState* st = ds.st;
     if (small_ok && out_skip == 0 && in_cap == 0 && out_cap == 0 && in_bytes + out_bytes <= kSmallCallBytes &&
         small_calls_on()) {
         if ((rc = ensure_pinned(st, std::max(in_bytes, out_bytes)))) return rc;
         std::memcpy(st->pin_in, x, in_bytes);
         std::string err;
         rc = launch(st->pin_in, st->pin_out, st->stream, &err);
-        if (rc) {
-            (void)hipStreamSynchronize(st->stream);
-            return fail(rc, err);
-        }
+        if (rc) return ds.drain_and_fail(rc, err);
         HIP_TRY(hipStreamSynchronize(st->stream));
         std::memcpy(y, st->pin_out, out_bytes);
         return FIR_OK;
@@ -194,10 +251,7 @@ int run_host(int device, const void* x, size_t in_bytes, void* y, size_t out_byt
     HIP_TRY(hipMemcpyAsync(st->in.ptr, x, in_bytes, hipMemcpyHostToDevice, st->stream));
     std::string err;
     rc = launch(st->in.ptr, st->out.ptr, st->stream, &err);
-    if (rc) {
-        (void)hipStreamSynchronize(st->stream);
-        return fail(rc, err);
-    }
+    if (rc) return ds.drain_and_fail(rc, err);
     HIP_TRY(hipMemcpyAsync(y, (char*)st->out.ptr + out_skip, out_bytes, hipMemcpyDeviceToHost, st->stream));
     HIP_TRY(hipStreamSynchronize(st->stream));
     return FIR_OK;
@@ -213,7 +267,6 @@ int run_host(int device, const void* x, size_t in_bytes, void* y, size_t out_byt
 // (halos inside the staged input, zero at the signal ends).  A u8 in-place call stays
 // correct: chunk i's output is copied back only after chunk i+1's input left the host.
 // FIR_HOST_CHUNKED=0 turns it off.
-constexpr int kChunks = DeviceState::kChunks;
 constexpr size_t kChunkedMinBytes = size_t(64) << 20;
 
 bool use_chunked(int64_t rows, int64_t n, int in_dtype) {
@@ -267,12 +320,10 @@ int run_host_chunked(int device, const void* x, int in_dtype, int64_t rows, int6
         return run_host(device, x, (size_t)n * isz, y, (size_t)n * osz, [&](void* dx, void* dy, hipStream_t s, std::string* err) {
             return fir::launch_fir1d_rows(dx, in_dtype, rows, width, ch, hq, taps, frac, acc, stage, dy, s, err);
         });
-    DeviceRestore restore;
-    DeviceState* st = nullptr;
-    int rc = device_state(device, &st);
+    DeviceSession ds(device);
+    int rc = ds.rc;
     if (rc) return rc;
-    std::lock_guard<std::mutex> lk(st->mu);
-    if ((rc = init_locked(st, device))) return rc;
+    DeviceState* st = ds.st;
     if ((rc = ensure(st->in, (size_t)n * isz)) || (rc = ensure(st->out, (size_t)n * osz))) return rc;
     const int64_t hl = (int64_t)(taps - 1 - taps / 2) * ch;
     char* dx = (char*)st->in.ptr;
@@ -364,19 +415,15 @@ bool mul_ok(int64_t a, int64_t b, int64_t* out) {
 // DMA that needs no host thread.  timing_ms (optional): FIR_TIMING_SLOTS values, see fir_hip.h.
 using PlaneReady = void (*)(void*, int);
 
-size_t align256(size_t v) { return (v + 255) / 256 * 256; }
-
 template <typename F>
 int run_host_images(int device, int n, const void* const* xs, const std::vector<size_t>& in_bytes, int np,
                     void* const* ys, const std::vector<size_t>& out_bytes, F launch, PlaneReady ready, void* ctx,
                     double* timing_ms) {
     const auto t_host0 = std::chrono::steady_clock::now();
-    DeviceRestore restore;
-    DeviceState* st = nullptr;
-    int rc = device_state(device, &st);
+    DeviceSession ds(device);
+    int rc = ds.rc;
     if (rc) return rc;
-    std::lock_guard<std::mutex> lk(st->mu);
-    if ((rc = init_locked(st, device))) return rc;
+    DeviceState* st = ds.st;
     std::vector<size_t> in_off(n), out_off(np);
     size_t in_total = 0, out_total = 0;
     for (int i = 0; i < n; ++i) {
@@ -399,22 +446,16 @@ int run_host_images(int device, int n, const void* const* xs, const std::vector<
     for (int i = 0; i < n; ++i) dx[i] = (const char*)st->in.ptr + in_off[i];
     for (int p = 0; p < np; ++p) dy[p] = (char*)st->out.ptr + out_off[p];
     hipStream_t s = st->stream;
-    // every copy and kernel already queued must finish before an error return: the caller may
-    // free its buffers, and the next call reuses the device buffers
-    auto bail = [&](int code, const std::string& msg) {
-        (void)hipStreamSynchronize(s);
-        return fail(code, msg);
-    };
     hipError_t e = hipSuccess;
     if (timing_ms) e = hipEventRecord(st->tev[0], s);
     for (int i = 0; i < n && e == hipSuccess; ++i)
         if (in_bytes[i]) e = hipMemcpyAsync((void*)dx[i], xs[i], in_bytes[i], hipMemcpyHostToDevice, s);
     if (e == hipSuccess && timing_ms) e = hipEventRecord(st->tev[1], s);
-    if (e != hipSuccess) return bail(FIR_EHIP, std::string("image upload: ") + hipGetErrorString(e));
+    if (e != hipSuccess) return ds.drain_and_fail(FIR_EHIP, std::string("image upload: ") + hipGetErrorString(e));
     std::string err;
-    if ((rc = launch(dx.data(), dy.data(), s, &err))) return bail(rc, err);
+    if ((rc = launch(dx.data(), dy.data(), s, &err))) return ds.drain_and_fail(rc, err);
     if (timing_ms && (e = hipEventRecord(st->tev[2], s)) != hipSuccess)
-        return bail(FIR_EHIP, std::string("hipEventRecord: ") + hipGetErrorString(e));
+        return ds.drain_and_fail(FIR_EHIP, std::string("hipEventRecord: ") + hipGetErrorString(e));
     // largest planes first: their writes (the caller's longest) start earliest, under the copies
     // of the small ones
     std::vector<int> order(np);
@@ -426,10 +467,10 @@ int run_host_images(int device, int n, const void* const* xs, const std::vector<
         if (e == hipSuccess) e = hipEventRecord(st->plane_ev[k], s);
     }
     if (e == hipSuccess && timing_ms) e = hipEventRecord(st->tev[3], s);
-    if (e != hipSuccess) return bail(FIR_EHIP, std::string("plane download: ") + hipGetErrorString(e));
+    if (e != hipSuccess) return ds.drain_and_fail(FIR_EHIP, std::string("plane download: ") + hipGetErrorString(e));
     for (int k = 0; k < np && ready; ++k) {
         if ((e = hipEventSynchronize(st->plane_ev[k])) != hipSuccess)
-            return bail(FIR_EHIP, std::string("plane download: ") + hipGetErrorString(e));
+            return ds.drain_and_fail(FIR_EHIP, std::string("plane download: ") + hipGetErrorString(e));
         ready(ctx, order[k]);
     }
     if ((e = hipStreamSynchronize(s)) != hipSuccess) return fail(FIR_EHIP, std::string("image batch: ") + hipGetErrorString(e));
@@ -464,6 +505,44 @@ int image_sizes(int n, const void* const* xs, const int64_t* rows, const int64_t
     return FIR_OK;
 }
 
+// Byte counts of a batch's images and of their `filters` output planes each (isz / osz bytes per
+// sample); false when every image is empty.
+bool batch_bytes(const std::vector<int64_t>& samples, int filters, size_t isz, size_t osz, std::vector<size_t>* ib,
+                 std::vector<size_t>* ob) {
+    bool any = false;
+    for (int64_t s : samples) {
+        any |= s != 0;
+        ib->push_back((size_t)s * isz);
+        ob->insert(ob->end(), (size_t)filters, (size_t)s * osz);
+    }
+    return any;
+}
+
+// fir_peer_access / fir_peer_atomics: `query(&ok, peer)` asks HIP about `device` and the device
+// behind `peer_bus_id`; a peer this process cannot see has no kernel path to it (*can = 0), the
+// device itself always does.
+template <typename Query>
+int peer_query(int device, const char* peer_bus_id, int* can, const char* what, Query query) {
+    return guarded([&]() -> int {
+        if (!peer_bus_id || !can) return fail(FIR_EINVAL, "NULL argument");
+        *can = 0;
+        int peer = -1;
+        if (hipDeviceGetByPCIBusId(&peer, peer_bus_id) != hipSuccess || peer < 0) {
+            (void)hipGetLastError();  // not visible to this process: no kernel path to it
+            return FIR_OK;
+        }
+        if (peer == device) {
+            *can = 1;
+            return FIR_OK;
+        }
+        int ok = 0;
+        hipError_t e = query(&ok, peer);
+        if (e != hipSuccess) return fail(FIR_EHIP, std::string(what) + ": " + hipGetErrorString(e));
+        *can = ok ? 1 : 0;
+        return FIR_OK;
+    });
+}
+
 }  // namespace
 
 extern "C" {
@@ -478,35 +557,32 @@ const char* fir_build_id(void) { return FIR_BUILD_ID; }
 const char* fir_last_error(void) { return g_err.c_str(); }
 
 int fir_device_count(int* count) {
-    if (!count) return fail(FIR_EINVAL, "count must not be NULL");
-    *count = 0;
-    int n = 0;
-    hipError_t e = hipGetDeviceCount(&n);
-    if (e != hipSuccess) return fail(FIR_ENODEV, std::string("hipGetDeviceCount: ") + hipGetErrorString(e));
-    *count = n;
-    return FIR_OK;
+    return guarded([&]() -> int {
+        if (!count) return fail(FIR_EINVAL, "count must not be NULL");
+        *count = 0;
+        int n = 0;
+        hipError_t e = hipGetDeviceCount(&n);
+        if (e != hipSuccess) return fail(FIR_ENODEV, std::string("hipGetDeviceCount: ") + hipGetErrorString(e));
+        *count = n;
+        return FIR_OK;
+    });
 }
 
 int fir1d_fixed_rows(const void* x, int in_dtype, int64_t rows, int64_t width, int channels, const int32_t* hq,
                      int taps, int frac_bits, int acc_bits, int out_stage, void* y, int device) {
-    try {
+    return guarded([&]() -> int {
         int64_t n = 0, rw = 0;
         if (channels < 1 || !mul_ok(rows, width, &rw) || !mul_ok(rw, channels, &n))
             return fail(FIR_EINVAL, "invalid rows/width/channels");
-        if (n == 0) {
-            std::string err;
-            // still validate the scalar arguments
-            int rc = fir::launch_fir1d_rows(nullptr, in_dtype, 0, 0, channels, hq, taps, frac_bits, acc_bits,
-                                            out_stage, nullptr, nullptr, &err);
-            return rc ? fail(rc, err) : FIR_OK;
-        }
+        const auto scalars = [&] {
+            return checked(fir::check_fir1d, in_dtype, 0, 0, channels, hq, taps, 1, frac_bits, acc_bits, out_stage);
+        };
+        if (n == 0) return scalars();
         if (!x || !y) return fail(FIR_EINVAL, "x and y must not be NULL");
         if (use_chunked(rows, n, in_dtype)) {
-            // scalar arguments validated by a zero-size launch first, as the unchunked path does
-            std::string err;
-            int rc = fir::launch_fir1d_rows(nullptr, in_dtype, 0, 0, channels, hq, taps, frac_bits, acc_bits,
-                                            out_stage, nullptr, nullptr, &err);
-            if (rc) return fail(rc, err);
+            // the chunked path refuses bad scalar arguments before it takes the device; the
+            // unchunked one leaves them to its launch
+            if (const int rc = scalars()) return rc;
             return run_host_chunked(device, x, in_dtype, rows, width, channels, hq, taps, frac_bits, acc_bits,
                                     out_stage, y);
         }
@@ -515,27 +591,21 @@ int fir1d_fixed_rows(const void* x, int in_dtype, int64_t rows, int64_t width, i
                             return fir::launch_fir1d_rows(dx, in_dtype, rows, width, channels, hq, taps, frac_bits,
                                                           acc_bits, out_stage, dy, s, err);
                         }, 0, 0, 0, true);
-    } catch (const std::exception& ex) {
-        return fail(FIR_EHIP, std::string("internal error: ") + ex.what());
-    } catch (...) {
-        return fail(FIR_EHIP, "internal error");
-    }
+    });
 }
 
 int fir1d_fixed_rows_sharded(const void* x, int in_dtype, int64_t rows, int64_t width, int channels,
                              const int32_t* hq, int taps, int frac_bits, int acc_bits, int out_stage, void* y,
                              const int* devices, int ndev) {
-    try {
+    return guarded([&]() -> int {
         if (ndev < 1 || !devices) return fail(FIR_EINVAL, "devices must list ndev >= 1 device ids");
         int64_t n = 0, rw = 0;
         if (channels < 1 || !mul_ok(rows, width, &rw) || !mul_ok(rw, channels, &n))
             return fail(FIR_EINVAL, "invalid rows/width/channels");
-        {
-            std::string err;  // the scalar arguments, once
-            int rc = fir::launch_fir1d_rows(nullptr, in_dtype, 0, 0, channels, hq, taps, frac_bits, acc_bits,
-                                            out_stage, nullptr, nullptr, &err);
-            if (rc) return fail(rc, err);
-        }
+        // the scalar arguments, once
+        if (const int rc = checked(fir::check_fir1d, in_dtype, 0, 0, channels, hq, taps, 1, frac_bits, acc_bits,
+            out_stage))
+            return rc;
         if (n == 0) return FIR_OK;
         if (!x || !y) return fail(FIR_EINVAL, "x and y must not be NULL");
         const size_t isz = in_size(in_dtype), osz = out_size(out_stage);
@@ -572,10 +642,10 @@ int fir1d_fixed_rows_sharded(const void* x, int in_dtype, int64_t rows, int64_t 
             std::string* msg = &msgs[wi];
             ++wi;
             workers.emplace_back([=]() noexcept {
-                try {
+                *rc = guarded([&]() -> int {  // never let an exception end the process
                     for (const Shard& sh : *list) {
                         const int64_t cnt = sh.rows * sh.width * channels;
-                        *rc = run_host(
+                        const int r = run_host(
                             dev, (const char*)x + sh.in0 * isz, (size_t)cnt * isz, (char*)y + sh.out0 * osz,
                             (size_t)sh.len * osz,
                             [&](void* dx, void* dy, hipStream_t s, std::string* err) {
@@ -583,123 +653,81 @@ int fir1d_fixed_rows_sharded(const void* x, int in_dtype, int64_t rows, int64_t 
                                                               frac_bits, acc_bits, out_stage, dy, s, err);
                             },
                             (size_t)sh.skip * osz, 0, (size_t)cnt * osz);
-                        if (*rc) {
-                            *msg = g_err;  // thread-local: this worker's message
-                            return;
-                        }
+                        if (r) return r;
                     }
-                } catch (const std::exception& ex) {  // never let an exception end the process
-                    *rc = FIR_EHIP;
-                    *msg = std::string("internal error: ") + ex.what();
-                } catch (...) {
-                    *rc = FIR_EHIP;
-                    *msg = "internal error";
-                }
+                    return FIR_OK;
+                });
+                if (*rc) *msg = g_err;  // thread-local: this worker's message
             });
         }
         for (auto& t : workers) t.join();
         for (size_t i = 0; i < rcs.size(); ++i)
             if (rcs[i]) return fail(rcs[i], msgs[i]);
         return FIR_OK;
-    } catch (const std::exception& ex) {
-        return fail(FIR_EHIP, std::string("internal error: ") + ex.what());
-    } catch (...) {
-        return fail(FIR_EHIP, "internal error");
-    }
+    });
 }
 
 int fir1d_fixed_rows_dev(const void* x_dev, int in_dtype, int64_t rows, int64_t width, int channels,
                          const int32_t* hq, int taps, int frac_bits, int acc_bits, int out_stage, void* y_dev,
                          void* stream) {
-    try {
-        std::string err;
-        int rc = fir::launch_fir1d_rows(x_dev, in_dtype, rows, width, channels, hq, taps, frac_bits, acc_bits,
-                                        out_stage, y_dev, (hipStream_t)stream, &err);
-        return rc ? fail(rc, err) : FIR_OK;
-    } catch (...) {
-        return fail(FIR_EHIP, "internal error");
-    }
+    return dev_entry(fir::launch_fir1d_rows, x_dev, in_dtype, rows, width, channels, hq, taps, frac_bits, acc_bits,
+                     out_stage, y_dev, (hipStream_t)stream);
 }
 
 int fir1d_fixed_rows_multi(const void* x, int in_dtype, int64_t rows, int64_t width, int channels,
                            const int32_t* hq, int taps, int filters, int frac_bits, int acc_bits, int out_stage,
                            void* y, int device) {
-    try {
+    return guarded([&]() -> int {
         int64_t n = 0, rw = 0, nf = 0;
         if (channels < 1 || filters < 1 || !mul_ok(rows, width, &rw) || !mul_ok(rw, channels, &n) ||
             !mul_ok(n, filters, &nf))
             return fail(FIR_EINVAL, "invalid rows/width/channels/filters");
-        if (n == 0) {
-            std::string err;
-            int rc = fir::launch_fir1d_rows_multi(nullptr, in_dtype, 0, 0, channels, hq, taps, filters, frac_bits,
-                                                  acc_bits, out_stage, nullptr, nullptr, &err);
-            return rc ? fail(rc, err) : FIR_OK;
-        }
+        if (n == 0)
+            return checked(fir::check_fir1d, in_dtype, 0, 0, channels, hq, taps, filters, frac_bits, acc_bits,
+                           out_stage);
         if (!x || !y) return fail(FIR_EINVAL, "x and y must not be NULL");
         return run_host(device, x, (size_t)n * in_size(in_dtype), y, (size_t)nf * out_size(out_stage),
                         [&](void* dx, void* dy, hipStream_t s, std::string* err) {
                             return fir::launch_fir1d_rows_multi(dx, in_dtype, rows, width, channels, hq, taps, filters,
                                                                 frac_bits, acc_bits, out_stage, dy, s, err);
                         }, 0, 0, 0, true);
-    } catch (...) {
-        return fail(FIR_EHIP, "internal error");
-    }
+    });
 }
 
 int fir1d_fixed_rows_multi_dev(const void* x_dev, int in_dtype, int64_t rows, int64_t width, int channels,
                                const int32_t* hq, int taps, int filters, int frac_bits, int acc_bits, int out_stage,
                                void* y_dev, void* stream) {
-    try {
-        std::string err;
-        int rc = fir::launch_fir1d_rows_multi(x_dev, in_dtype, rows, width, channels, hq, taps, filters, frac_bits,
-                                              acc_bits, out_stage, y_dev, (hipStream_t)stream, &err);
-        return rc ? fail(rc, err) : FIR_OK;
-    } catch (...) {
-        return fail(FIR_EHIP, "internal error");
-    }
+    return dev_entry(fir::launch_fir1d_rows_multi, x_dev, in_dtype, rows, width, channels, hq, taps, filters, frac_bits,
+                     acc_bits, out_stage, y_dev, (hipStream_t)stream);
 }
 
 int fir1d_fixed_images_multi_dev(int n_images, const void* const* x_devs, const int64_t* rows, const int64_t* widths,
                                  int in_dtype, int channels, const int32_t* hq, int taps, int filters, int frac_bits,
                                  int acc_bits, int out_stage, void* const* y_planes, void* stream) {
-    try {
-        std::string err;
+    return dev_entry([&](std::string* err) -> int {
         int64_t rw = 0, n = 0;
         for (int i = 0; i < n_images && rows && widths; ++i)
             if (!mul_ok(rows[i], widths[i], &rw) || !mul_ok(rw, channels < 1 ? 1 : channels, &n))
-                return fail(FIR_EINVAL, "image " + std::to_string(i) + ": invalid rows/width/channels");
-        int rc = fir::launch_fir1d_images_multi(n_images, x_devs, rows, widths, in_dtype, channels, hq, taps, filters,
-                                                frac_bits, acc_bits, out_stage, y_planes, (hipStream_t)stream, &err);
-        return rc ? fail(rc, err) : FIR_OK;
-    } catch (...) {
-        return fail(FIR_EHIP, "internal error");
-    }
+                return *err = "image " + std::to_string(i) + ": invalid rows/width/channels", FIR_EINVAL;
+        return fir::launch_fir1d_images_multi(n_images, x_devs, rows, widths, in_dtype, channels, hq, taps, filters,
+                                              frac_bits, acc_bits, out_stage, y_planes, (hipStream_t)stream, err);
+    });
 }
 
 int fir1d_fixed_images_multi(int n_images, const void* const* xs, const int64_t* rows, const int64_t* widths,
                              int in_dtype, int channels, const int32_t* hq, int taps, int filters, int frac_bits,
                              int acc_bits, int out_stage, void* const* y_planes, int device, fir_plane_ready_fn ready,
                              void* ready_ctx, double* timing_ms) {
-    try {
+    return guarded([&]() -> int {
         if (channels < 1) return fail(FIR_EINVAL, "channels must be >= 1");
         std::vector<int64_t> samples;
         int rc = image_sizes(n_images, xs, rows, widths, channels, filters, y_planes, &samples);
         if (rc) return rc;
-        {
-            std::string err;  // the scalar arguments, before any device work
-            rc = fir::launch_fir1d_rows_multi(nullptr, in_dtype, 0, 0, channels, hq, taps, filters, frac_bits, acc_bits,
-                                              out_stage, nullptr, nullptr, &err);
-            if (rc) return fail(rc, err);
-        }
-        int64_t total = 0;
-        for (int64_t s : samples) total += s;
-        if (total == 0) return FIR_OK;
-        const size_t isz = in_size(in_dtype), osz = out_size(out_stage);
-        std::vector<size_t> ib(n_images), ob((size_t)n_images * filters);
-        for (int i = 0; i < n_images; ++i) {
-            ib[i] = (size_t)samples[i] * isz;
-            for (int f = 0; f < filters; ++f) ob[(size_t)i * filters + f] = (size_t)samples[i] * osz;
-        }
+        // the scalar arguments, before any device work
+        rc = checked(fir::check_fir1d, in_dtype, 0, 0, channels, hq, taps, filters, frac_bits, acc_bits, out_stage);
+        if (rc) return rc;
+        std::vector<size_t> ib, ob;
+        if (!batch_bytes(samples, filters, in_size(in_dtype), out_size(out_stage), &ib, &ob)) return FIR_OK;
         return run_host_images(
             device, n_images, xs, ib, n_images * filters, y_planes, ob,
             [&](const void* const* dx, void* const* dy, hipStream_t s, std::string* err) {
@@ -707,59 +735,37 @@ int fir1d_fixed_images_multi(int n_images, const void* const* xs, const int64_t*
                                                       frac_bits, acc_bits, out_stage, dy, s, err);
             },
             ready, ready_ctx, timing_ms);
-    } catch (const std::exception& ex) {
-        return fail(FIR_EHIP, std::string("internal error: ") + ex.what());
-    } catch (...) {
-        return fail(FIR_EHIP, "internal error");
-    }
+    });
 }
 
 int fir1d_fixed_edges_dev(const void* x_dev, int in_dtype, int64_t n, int channels, const int32_t* hq, int taps,
                           int frac_bits, int acc_bits, int out_stage, const void* halo_left_dev,
                           const void* halo_right_dev, void* y_dev, void* stream) {
-    try {
-        std::string err;
-        int rc = fir::launch_fir1d_edges(x_dev, in_dtype, n, channels, hq, taps, frac_bits, acc_bits, out_stage,
-                                         halo_left_dev, halo_right_dev, y_dev, (hipStream_t)stream, &err);
-        return rc ? fail(rc, err) : FIR_OK;
-    } catch (...) {
-        return fail(FIR_EHIP, "internal error");
-    }
+    return dev_entry(fir::launch_fir1d_edges, x_dev, in_dtype, n, channels, hq, taps, frac_bits, acc_bits, out_stage,
+                     halo_left_dev, halo_right_dev, y_dev, (hipStream_t)stream);
 }
 
 int fir1d_fixed_segment_dev(const void* x_dev, int in_dtype, int64_t n, int channels, const int32_t* hq, int taps,
                             int frac_bits, int acc_bits, int out_stage, const void* halo_left_dev,
                             const void* halo_right_dev, void* y_dev, void* stream) {
-    try {
-        std::string err;
-        int rc = fir::launch_fir1d_segment(x_dev, in_dtype, n, channels, hq, taps, frac_bits, acc_bits, out_stage,
-                                           halo_left_dev, halo_right_dev, y_dev, (hipStream_t)stream, &err);
-        return rc ? fail(rc, err) : FIR_OK;
-    } catch (...) {
-        return fail(FIR_EHIP, "internal error");
-    }
+    return dev_entry(fir::launch_fir1d_segment, x_dev, in_dtype, n, channels, hq, taps, frac_bits, acc_bits, out_stage,
+                     halo_left_dev, halo_right_dev, y_dev, (hipStream_t)stream);
 }
 
 int fir2d_fixed_frames(const uint8_t* x, int64_t frames, int64_t height, int64_t width, const int32_t* hq,
                        int tap_rows, int tap_cols, int frac_bits, int acc_bits, int out_stage, void* y, int device) {
-    try {
+    return guarded([&]() -> int {
         int64_t n = 0, hw = 0;
         if (!mul_ok(height, width, &hw) || !mul_ok(hw, frames, &n)) return fail(FIR_EINVAL, "invalid frames/height/width");
-        if (n == 0) {
-            std::string err;
-            int rc = fir::launch_fir2d(nullptr, 0, 0, 0, hq, tap_rows, tap_cols, frac_bits, acc_bits, out_stage,
-                                       nullptr, nullptr, &err);
-            return rc ? fail(rc, err) : FIR_OK;
-        }
+        if (n == 0)  // an empty problem: the taps and the stage alone
+            return checked(fir::check_fir2d, 0, 0, 0, hq, tap_rows, tap_cols, frac_bits, acc_bits, out_stage);
         if (!x || !y) return fail(FIR_EINVAL, "x and y must not be NULL");
         return run_host(device, x, (size_t)n, y, (size_t)n * out_size(out_stage),
                         [&](void* dx, void* dy, hipStream_t s, std::string* err) {
                             return fir::launch_fir2d((const uint8_t*)dx, frames, height, width, hq, tap_rows, tap_cols,
                                                      frac_bits, acc_bits, out_stage, dy, s, err);
                         });
-    } catch (...) {
-        return fail(FIR_EHIP, "internal error");
-    }
+    });
 }
 
 int fir2d_fixed(const uint8_t* x, int64_t height, int64_t width, const int32_t* hq, int tap_rows, int tap_cols,
@@ -770,14 +776,8 @@ int fir2d_fixed(const uint8_t* x, int64_t height, int64_t width, const int32_t* 
 int fir2d_fixed_frames_dev(const uint8_t* x_dev, int64_t frames, int64_t height, int64_t width, const int32_t* hq,
                            int tap_rows, int tap_cols, int frac_bits, int acc_bits, int out_stage, void* y_dev,
                            void* stream) {
-    try {
-        std::string err;
-        int rc = fir::launch_fir2d(x_dev, frames, height, width, hq, tap_rows, tap_cols, frac_bits, acc_bits, out_stage,
-                                   y_dev, (hipStream_t)stream, &err);
-        return rc ? fail(rc, err) : FIR_OK;
-    } catch (...) {
-        return fail(FIR_EHIP, "internal error");
-    }
+    return dev_entry(fir::launch_fir2d, x_dev, frames, height, width, hq, tap_rows, tap_cols, frac_bits, acc_bits,
+                     out_stage, y_dev, (hipStream_t)stream);
 }
 
 int fir2d_fixed_dev(const uint8_t* x_dev, int64_t height, int64_t width, const int32_t* hq, int tap_rows,
@@ -788,39 +788,26 @@ int fir2d_fixed_dev(const uint8_t* x_dev, int64_t height, int64_t width, const i
 
 int fir1d_ideal_rows(const uint8_t* x, int64_t rows, int64_t width, const double* h, int taps, double* y,
                      int device) {
-    try {
+    return guarded([&]() -> int {
         int64_t n = 0;
         if (!mul_ok(rows, width, &n)) return fail(FIR_EINVAL, "invalid rows/width");
-        if (n == 0) {
-            std::string err;
-            int rc = fir::launch_fir1d_ideal(nullptr, 0, 0, h, taps, nullptr, nullptr, &err);
-            return rc ? fail(rc, err) : FIR_OK;
-        }
+        if (n == 0) return checked(fir::check_fir1d_ideal, 0, 0, h, taps);
         if (!x || !y) return fail(FIR_EINVAL, "x and y must not be NULL");
         return run_host(device, x, (size_t)n, y, (size_t)n * 8, [&](void* dx, void* dy, hipStream_t s, std::string* err) {
             return fir::launch_fir1d_ideal((const uint8_t*)dx, rows, width, h, taps, (double*)dy, s, err);
         }, 0, 0, 0, true);
-    } catch (...) {
-        return fail(FIR_EHIP, "internal error");
-    }
+    });
 }
 
 int fir1d_ideal_rows_dev(const uint8_t* x_dev, int64_t rows, int64_t width, const double* h, int taps,
                          double* y_dev, void* stream) {
-    try {
-        std::string err;
-        int rc = fir::launch_fir1d_ideal(x_dev, rows, width, h, taps, y_dev, (hipStream_t)stream, &err);
-        return rc ? fail(rc, err) : FIR_OK;
-    } catch (...) {
-        return fail(FIR_EHIP, "internal error");
-    }
+    return dev_entry(fir::launch_fir1d_ideal, x_dev, rows, width, h, taps, y_dev, (hipStream_t)stream);
 }
 
 int fir2d_ideal_frames(const uint8_t* x, int64_t frames, int64_t height, int64_t width, const double* h, int tap_rows,
                        int tap_cols, double* y, int device) {
-    try {
-        std::string err;
-        if (const int rc = fir::check_fir2d_ideal(frames, height, width, h, tap_rows, tap_cols, &err)) return fail(rc, err);
+    return guarded([&]() -> int {
+        if (const int rc = checked(fir::check_fir2d_ideal, frames, height, width, h, tap_rows, tap_cols)) return rc;
         int64_t n = 0, hw = 0;
         if (!mul_ok(height, width, &hw) || !mul_ok(hw, frames, &n) || n > INT64_MAX / 8)
             return fail(FIR_EINVAL, "invalid frames/height/width");
@@ -830,9 +817,7 @@ int fir2d_ideal_frames(const uint8_t* x, int64_t frames, int64_t height, int64_t
             return fir::launch_fir2d_ideal((const uint8_t*)dx, frames, height, width, h, tap_rows, tap_cols, (double*)dy,
                                            s, e);
         });
-    } catch (...) {
-        return fail(FIR_EHIP, "internal error");
-    }
+    });
 }
 
 int fir2d_ideal(const uint8_t* x, int64_t height, int64_t width, const double* h, int tap_rows, int tap_cols, double* y,
@@ -842,14 +827,8 @@ int fir2d_ideal(const uint8_t* x, int64_t height, int64_t width, const double* h
 
 int fir2d_ideal_frames_dev(const uint8_t* x_dev, int64_t frames, int64_t height, int64_t width, const double* h,
                            int tap_rows, int tap_cols, double* y_dev, void* stream) {
-    try {
-        std::string err;
-        int rc = fir::launch_fir2d_ideal(x_dev, frames, height, width, h, tap_rows, tap_cols, y_dev, (hipStream_t)stream,
-                                         &err);
-        return rc ? fail(rc, err) : FIR_OK;
-    } catch (...) {
-        return fail(FIR_EHIP, "internal error");
-    }
+    return dev_entry(fir::launch_fir2d_ideal, x_dev, frames, height, width, h, tap_rows, tap_cols, y_dev,
+                     (hipStream_t)stream);
 }
 
 int fir2d_ideal_dev(const uint8_t* x_dev, int64_t height, int64_t width, const double* h, int tap_rows, int tap_cols,
@@ -860,25 +839,18 @@ int fir2d_ideal_dev(const uint8_t* x_dev, int64_t height, int64_t width, const d
 int fir1d_ideal_images_multi(int n_images, const uint8_t* const* xs, const int64_t* rows, const int64_t* widths,
                              const double* h, int taps, int filters, double* const* y_planes, int device,
                              fir_plane_ready_fn ready, void* ready_ctx, double* timing_ms) {
-    try {
+    return guarded([&]() -> int {
         std::vector<int64_t> samples;
         int rc = image_sizes(n_images, (const void* const*)xs, rows, widths, 1, filters, (void* const*)y_planes,
                              &samples);
         if (rc) return rc;
         for (int f = 0; f < filters; ++f) {  // every filter's taps, before any device work
             std::string err;
-            rc = fir::launch_fir1d_ideal(nullptr, 0, 0, h ? h + (size_t)f * (taps > 0 ? taps : 0) : nullptr, taps,
-                                         nullptr, nullptr, &err);
+            rc = fir::check_fir1d_ideal(0, 0, h ? h + (size_t)f * (taps > 0 ? taps : 0) : nullptr, taps, &err);
             if (rc) return fail(rc, "filter " + std::to_string(f) + ": " + err);
         }
-        int64_t total = 0;
-        for (int64_t s : samples) total += s;
-        if (total == 0) return FIR_OK;
-        std::vector<size_t> ib(n_images), ob((size_t)n_images * filters);
-        for (int i = 0; i < n_images; ++i) {
-            ib[i] = (size_t)samples[i];
-            for (int f = 0; f < filters; ++f) ob[(size_t)i * filters + f] = (size_t)samples[i] * sizeof(double);
-        }
+        std::vector<size_t> ib, ob;
+        if (!batch_bytes(samples, filters, 1, sizeof(double), &ib, &ob)) return FIR_OK;
         return run_host_images(
             device, n_images, (const void* const*)xs, ib, n_images * filters, (void* const*)y_planes, ob,
             [&](const void* const* dx, void* const* dy, hipStream_t s, std::string* err) {
@@ -894,15 +866,11 @@ int fir1d_ideal_images_multi(int n_images, const uint8_t* const* xs, const int64
                 return (int)FIR_OK;
             },
             ready, ready_ctx, timing_ms);
-    } catch (const std::exception& ex) {
-        return fail(FIR_EHIP, std::string("internal error: ") + ex.what());
-    } catch (...) {
-        return fail(FIR_EHIP, "internal error");
-    }
+    });
 }
 
 int fir_host_alloc(int64_t bytes, void** out) {
-    try {
+    return guarded([&]() -> int {
         if (!out || bytes < 0) return fail(FIR_EINVAL, "invalid arguments");
         *out = nullptr;
         if (bytes == 0) return FIR_OK;
@@ -912,33 +880,33 @@ int fir_host_alloc(int64_t bytes, void** out) {
             return fail(FIR_ENOMEM, "hipHostMalloc(" + std::to_string(bytes) + "): " + hipGetErrorString(e));
         }
         return FIR_OK;
-    } catch (...) {
-        return fail(FIR_EHIP, "internal error");
-    }
+    });
 }
 
 int fir_host_free(void* p) {
-    if (!p) return FIR_OK;
-    hipError_t e = hipHostFree(p);
-    return e == hipSuccess ? FIR_OK : fail(FIR_EHIP, std::string("hipHostFree: ") + hipGetErrorString(e));
+    return guarded([&]() -> int {
+        if (!p) return FIR_OK;
+        hipError_t e = hipHostFree(p);
+        return e == hipSuccess ? FIR_OK : fail(FIR_EHIP, std::string("hipHostFree: ") + hipGetErrorString(e));
+    });
 }
 
-int64_t fir_metrics_work_bytes(int64_t n) { return (int64_t)fir::metrics_work_bytes(n); }
+int64_t fir_metrics_work_bytes(int64_t n) {
+    return guarded_size([&] { return fir::metrics_work_bytes(n); });
+}
 
 int fir_compare_metrics(const double* ideal, const void* fixed, int fixed_dtype, int64_t n, double* out,
                         int device) {
-    try {
+    return guarded([&]() -> int {
         if (n < 0 || !out || (n > 0 && (!ideal || !fixed))) return fail(FIR_EINVAL, "invalid arguments");
         const int es = fir::metrics_dtype_size(fixed_dtype);
         if (!es) return fail(FIR_EINVAL, "unknown fixed dtype");
-        DeviceRestore restore;
-        DeviceState* st = nullptr;
-        int rc = device_state(device, &st);
+        DeviceSession ds(device);
+        int rc = ds.rc;
         if (rc) return rc;
-        std::lock_guard<std::mutex> lk(st->mu);
-        if ((rc = init_locked(st, device))) return rc;
+        DeviceState* st = ds.st;
         const size_t ib = (size_t)n * 8, fb = (size_t)n * es;
-        const size_t fo = (ib + 255) / 256 * 256;
+        const size_t fo = align256(ib);  // device input = ideal, then fixed on a 256-byte boundary
         if ((rc = ensure(st->in, fo + fb + 1)) || (rc = ensure(st->out, fir::metrics_work_bytes(n) + 256))) return rc;
         char* din = (char*)st->in.ptr;
         if (n > 0) {
@@ -949,58 +917,37 @@ int fir_compare_metrics(const double* ideal, const void* fixed, int fixed_dtype,
         std::string err;
         rc = fir::launch_metrics((const double*)din, din + fo, fixed_dtype, n, dout, (char*)st->out.ptr + 256,
                                  st->stream, &err);
-        if (rc) {
-            (void)hipStreamSynchronize(st->stream);
-            return fail(rc, err);
-        }
+        if (rc) return ds.drain_and_fail(rc, err);
         HIP_TRY(hipMemcpyAsync(out, dout, 9 * sizeof(double), hipMemcpyDeviceToHost, st->stream));
         HIP_TRY(hipStreamSynchronize(st->stream));
         if (out[8] != 0.0) return fail(FIR_EHIP, "metrics: the in-kernel hand-off timed out");
         return FIR_OK;
-    } catch (...) {
-        return fail(FIR_EHIP, "internal error");
-    }
+    });
 }
 
 int fir_compare_metrics_dev(const double* ideal_dev, const void* fixed_dev, int fixed_dtype, int64_t n,
                             double* out_dev, void* work_dev, void* stream) {
-    try {
-        std::string err;
-        int rc = fir::launch_metrics(ideal_dev, fixed_dev, fixed_dtype, n, out_dev, work_dev, (hipStream_t)stream, &err);
-        return rc ? fail(rc, err) : FIR_OK;
-    } catch (...) {
-        return fail(FIR_EHIP, "internal error");
-    }
+    return dev_entry(fir::launch_metrics, ideal_dev, fixed_dev, fixed_dtype, n, out_dev, work_dev, (hipStream_t)stream);
 }
 
-int64_t fir_restore_work_bytes(void) { return (int64_t)fir::restore_work_bytes(); }
+int64_t fir_restore_work_bytes(void) {
+    return guarded_size([] { return fir::restore_work_bytes(); });
+}
 
 int fir_restore_u8(const double* a, int64_t n, int policy, uint8_t* out, int device) {
-    try {
+    return guarded([&]() -> int {
         if (n < 0 || (n > 0 && (!a || !out))) return fail(FIR_EINVAL, "invalid arguments");
-        if (n == 0) {
-            std::string err;
-            int rc = fir::launch_restore_u8(nullptr, 0, policy, nullptr, nullptr, nullptr, &err);
-            return rc ? fail(rc, err) : FIR_OK;
-        }
-        const size_t ab = (size_t)n * 8, wo = (ab + 255) / 256 * 256;
+        if (n == 0) return checked(fir::check_restore_u8, 0, policy);
+        const size_t ab = (size_t)n * 8, wo = align256(ab);
         // device input = a, then the normalize scratch
         return run_host(device, a, ab, out, (size_t)n, [&](void* da, void* dout, hipStream_t s, std::string* err) {
             return fir::launch_restore_u8((const double*)da, n, policy, (uint8_t*)dout, (char*)da + wo, s, err);
         }, 0, wo + fir::restore_work_bytes());
-    } catch (...) {
-        return fail(FIR_EHIP, "internal error");
-    }
+    });
 }
 
 int fir_restore_u8_dev(const double* a_dev, int64_t n, int policy, uint8_t* out_dev, void* work_dev, void* stream) {
-    try {
-        std::string err;
-        int rc = fir::launch_restore_u8(a_dev, n, policy, out_dev, work_dev, (hipStream_t)stream, &err);
-        return rc ? fail(rc, err) : FIR_OK;
-    } catch (...) {
-        return fail(FIR_EHIP, "internal error");
-    }
+    return dev_entry(fir::launch_restore_u8, a_dev, n, policy, out_dev, work_dev, (hipStream_t)stream);
 }
 
 // ---- xGMI peer halos (fir_hip.h) --------------------------------------------------------
@@ -1012,7 +959,7 @@ std::map<void*, void*> g_ipc_base;  // pointer handed out by fir_ipc_import -> m
 }  // namespace
 
 int fir_ipc_export(const void* dev_ptr, void* handle_out, int64_t* offset_out) {
-    try {
+    return guarded([&]() -> int {
         if (!dev_ptr || !handle_out || !offset_out) return fail(FIR_EINVAL, "NULL argument");
         hipDeviceptr_t base = nullptr;
         size_t size = 0;
@@ -1024,13 +971,11 @@ int fir_ipc_export(const void* dev_ptr, void* handle_out, int64_t* offset_out) {
         std::memcpy(handle_out, &h, sizeof(h));
         *offset_out = (int64_t)((const char*)dev_ptr - (const char*)base);
         return FIR_OK;
-    } catch (...) {
-        return fail(FIR_EHIP, "internal error");
-    }
+    });
 }
 
 int fir_ipc_import(const void* handle, int64_t offset, int device, void** dev_ptr_out) {
-    try {
+    return guarded([&]() -> int {
         if (!handle || !dev_ptr_out || offset < 0) return fail(FIR_EINVAL, "invalid argument");
         *dev_ptr_out = nullptr;
         DeviceRestore restore;
@@ -1046,13 +991,11 @@ int fir_ipc_import(const void* handle, int64_t offset, int device, void** dev_pt
         g_ipc_base[p] = base;
         *dev_ptr_out = p;
         return FIR_OK;
-    } catch (...) {
-        return fail(FIR_EHIP, "internal error");
-    }
+    });
 }
 
 int fir_ipc_close(void* dev_ptr) {
-    try {
+    return guarded([&]() -> int {
         void* base = nullptr;
         {
             std::lock_guard<std::mutex> g(g_ipc_mu);
@@ -1064,111 +1007,58 @@ int fir_ipc_close(void* dev_ptr) {
         hipError_t e = hipIpcCloseMemHandle(base);
         if (e != hipSuccess) return fail(FIR_EHIP, std::string("hipIpcCloseMemHandle: ") + hipGetErrorString(e));
         return FIR_OK;
-    } catch (...) {
-        return fail(FIR_EHIP, "internal error");
-    }
+    });
 }
 
 int fir_device_bus_id(int device, char* out, int len) {
-    try {
+    return guarded([&]() -> int {
         if (!out || len < 16) return fail(FIR_EINVAL, "out must hold at least 16 bytes");
         out[0] = 0;
         hipError_t e = hipDeviceGetPCIBusId(out, len, device);
         if (e != hipSuccess) return fail(FIR_ENODEV, std::string("hipDeviceGetPCIBusId: ") + hipGetErrorString(e));
         return FIR_OK;
-    } catch (...) {
-        return fail(FIR_EHIP, "internal error");
-    }
+    });
 }
 
 int fir_peer_access(int device, const char* peer_bus_id, int* can) {
-    try {
-        if (!peer_bus_id || !can) return fail(FIR_EINVAL, "NULL argument");
-        *can = 0;
-        int peer = -1;
-        if (hipDeviceGetByPCIBusId(&peer, peer_bus_id) != hipSuccess || peer < 0) {
-            (void)hipGetLastError();  // not visible to this process: no kernel path to it
-            return FIR_OK;
-        }
-        if (peer == device) {
-            *can = 1;
-            return FIR_OK;
-        }
-        int ok = 0;
-        hipError_t e = hipDeviceCanAccessPeer(&ok, device, peer);
-        if (e != hipSuccess) return fail(FIR_EHIP, std::string("hipDeviceCanAccessPeer: ") + hipGetErrorString(e));
-        *can = ok ? 1 : 0;
-        return FIR_OK;
-    } catch (...) {
-        return fail(FIR_EHIP, "internal error");
-    }
+    return peer_query(device, peer_bus_id, can, "hipDeviceCanAccessPeer",
+                      [&](int* ok, int peer) { return hipDeviceCanAccessPeer(ok, device, peer); });
 }
 
 int fir_peer_atomics(int device, const char* peer_bus_id, int* can) {
-    try {
-        if (!peer_bus_id || !can) return fail(FIR_EINVAL, "NULL argument");
-        *can = 0;
-        int peer = -1;
-        if (hipDeviceGetByPCIBusId(&peer, peer_bus_id) != hipSuccess || peer < 0) {
-            (void)hipGetLastError();
-            return FIR_OK;
-        }
-        if (peer == device) {
-            *can = 1;
-            return FIR_OK;
-        }
-        int ok = 0;
-        hipError_t e = hipDeviceGetP2PAttribute(&ok, hipDevP2PAttrNativeAtomicSupported, device, peer);
-        if (e != hipSuccess) return fail(FIR_EHIP, std::string("hipDeviceGetP2PAttribute: ") + hipGetErrorString(e));
-        *can = ok ? 1 : 0;
-        return FIR_OK;
-    } catch (...) {
-        return fail(FIR_EHIP, "internal error");
-    }
+    return peer_query(device, peer_bus_id, can, "hipDeviceGetP2PAttribute", [&](int* ok, int peer) {
+        return hipDeviceGetP2PAttribute(ok, hipDevP2PAttrNativeAtomicSupported, device, peer);
+    });
 }
 
 int64_t fir_halo_mailbox_bytes(int64_t halo_left_bytes, int64_t halo_right_bytes) {
     if (halo_left_bytes < 0 || halo_right_bytes < 0) return -1;
-    return fir::halo_mailbox_bytes(halo_left_bytes, halo_right_bytes);
+    return guarded_size([&] { return fir::halo_mailbox_bytes(halo_left_bytes, halo_right_bytes); });
 }
 
 int fir_halo_mailbox_init_dev(void* mailbox_dev, int64_t bytes, int64_t halo_left_bytes, int64_t halo_right_bytes,
                               void* stream) {
-    try {
-        std::string err;
-        int rc = fir::launch_halo_mailbox_init(mailbox_dev, bytes, halo_left_bytes, halo_right_bytes,
-                                               (hipStream_t)stream, &err);
-        return rc ? fail(rc, err) : FIR_OK;
-    } catch (...) {
-        return fail(FIR_EHIP, "internal error");
-    }
+    return dev_entry(fir::launch_halo_mailbox_init, mailbox_dev, bytes, halo_left_bytes, halo_right_bytes,
+                     (hipStream_t)stream);
 }
 
 int fir_halo_gate_dev(const void* x_dev, int64_t seg_bytes, int64_t halo_left_bytes, int64_t halo_right_bytes,
                       void* mailbox_dev, const void* left_mailbox_dev, const void* right_mailbox_dev,
                       void* halo_left_dev, void* halo_right_dev, int32_t* status_dev, double timeout_s,
                       void* stream) {
-    try {
-        std::string err;
-        int rc = fir::launch_halo_gate(x_dev, seg_bytes, halo_left_bytes, halo_right_bytes, mailbox_dev,
-                                       left_mailbox_dev, right_mailbox_dev, halo_left_dev, halo_right_dev, status_dev,
-                                       timeout_s, (hipStream_t)stream, &err);
-        return rc ? fail(rc, err) : FIR_OK;
-    } catch (...) {
-        return fail(FIR_EHIP, "internal error");
-    }
+    return dev_entry(fir::launch_halo_gate, x_dev, seg_bytes, halo_left_bytes, halo_right_bytes, mailbox_dev,
+                     left_mailbox_dev, right_mailbox_dev, halo_left_dev, halo_right_dev, status_dev, timeout_s,
+                     (hipStream_t)stream);
 }
 
 int fir_peek(const void* dev_ptr, void* host_out, int64_t bytes) {
-    try {
+    return guarded([&]() -> int {
         if (bytes < 0 || (bytes > 0 && (!dev_ptr || !host_out))) return fail(FIR_EINVAL, "invalid argument");
         if (bytes == 0) return FIR_OK;
         hipError_t e = hipMemcpy(host_out, dev_ptr, (size_t)bytes, hipMemcpyDeviceToHost);
         if (e != hipSuccess) return fail(FIR_EHIP, std::string("hipMemcpy: ") + hipGetErrorString(e));
         return FIR_OK;
-    } catch (...) {
-        return fail(FIR_EHIP, "internal error");
-    }
+    });
 }
 
 }  // extern "C"

@@ -27,6 +27,7 @@
 
 #include "fir1d_reg_launch.h"
 #include "fir_common.h"
+#include "fir_dispatch.h"
 #include "fir_launch.h"
 
 // Long filters (beyond the register kernel's 9 taps) take the int8 matrix-core kernel
@@ -190,18 +191,10 @@ static hipError_t dispatch_generic(int in_dtype, int stage, const void* x, void*
                                    int64_t total, int64_t rowlen, bool multi_row, int ch, const void* hl,
                                    const void* hr, const int32_t* hq, int L, int frac, int acc_bits,
                                    hipStream_t s) {
-    if (in_dtype == FIR_IN_U8) {
-        return stage == FIR_OUT_U8_SAT
-                   ? launch_generic<uint8_t, FIR_OUT_U8_SAT>(x, y, start, end, total, rowlen, multi_row, ch, hl,
-                                                             hr, hq, L, frac, acc_bits, s)
-                   : launch_generic<uint8_t, FIR_OUT_I32>(x, y, start, end, total, rowlen, multi_row, ch, hl, hr,
-                                                          hq, L, frac, acc_bits, s);
-    }
-    return stage == FIR_OUT_U8_SAT
-               ? launch_generic<int16_t, FIR_OUT_U8_SAT>(x, y, start, end, total, rowlen, multi_row, ch, hl, hr,
-                                                         hq, L, frac, acc_bits, s)
-               : launch_generic<int16_t, FIR_OUT_I32>(x, y, start, end, total, rowlen, multi_row, ch, hl, hr, hq,
-                                                      L, frac, acc_bits, s);
+    return with_io(in_dtype, stage, [&](auto t, auto st) {
+        return launch_generic<typename decltype(t)::type, st>(x, y, start, end, total, rowlen, multi_row, ch, hl, hr,
+                                                              hq, L, frac, acc_bits, s);
+    });
 }
 
 template <typename InT, int STAGE>
@@ -220,8 +213,9 @@ static hipError_t launch_edges(const void* x, void* y, int64_t total, int ch, co
     return hipGetLastError();
 }
 
-static int check_common(int in_dtype, int64_t rows, int64_t width, int ch, const int32_t* hq, int L, int frac,
-                        int acc_bits, int stage, std::string* err) {
+int check_fir1d(int in_dtype, int64_t rows, int64_t width, int ch, const int32_t* hq, int L, int F, int frac,
+                int acc_bits, int stage, std::string* err) {
+    if (F < 1) return *err = "filters must be >= 1", FIR_EINVAL;
     if (in_dtype != FIR_IN_U8 && in_dtype != FIR_IN_I16) return *err = "in_dtype must be FIR_IN_U8 or FIR_IN_I16", FIR_EINVAL;
     if (stage != FIR_OUT_U8_SAT && stage != FIR_OUT_I32) return *err = "out_stage must be FIR_OUT_U8_SAT or FIR_OUT_I32", FIR_EINVAL;
     if (rows < 0 || width < 0) return *err = "rows and width must be >= 0", FIR_EINVAL;
@@ -243,9 +237,19 @@ static bool reg_path_ok(const void* x, const void* y, int in_dtype, int64_t rows
            (rows == 1 || (rowlen >= vec + (L - 1) * ch && total < ((int64_t)1 << 32)));
 }
 
+// One filter on the register kernel (reg_path_ok holds); hl / hr: a single-row segment's halos.
+static hipError_t launch_reg_one(int in_dtype, int stage, int ch, int L, const void* x, void* y, int64_t rows,
+                                 int64_t total, int64_t rowlen, const int32_t* hq, int frac, int acc_bits,
+                                 hipStream_t s, const void* hl = nullptr, const void* hr = nullptr) {
+    return with_reg_config(in_dtype, stage, ch, [&](auto t, auto st, auto c) {
+        return launch_reg_taps<typename decltype(t)::type, st, c, 1>(L, x, y, rows, total, rowlen, hq, frac, acc_bits, s,
+                                                                     hl, hr);
+    });
+}
+
 int launch_fir1d_rows(const void* x, int in_dtype, int64_t rows, int64_t width, int ch, const int32_t* hq, int L,
                       int frac, int acc_bits, int stage, void* y, hipStream_t stream, std::string* err) {
-    int rc = check_common(in_dtype, rows, width, ch, hq, L, frac, acc_bits, stage, err);
+    int rc = check_fir1d(in_dtype, rows, width, ch, hq, L, 1, frac, acc_bits, stage, err);
     if (rc) return rc;
     const int64_t rowlen = width * ch;
     const int64_t total = rows * rowlen;
@@ -253,19 +257,7 @@ int launch_fir1d_rows(const void* x, int in_dtype, int64_t rows, int64_t width, 
     if (!x || !y) return *err = "x and y must not be NULL", FIR_EINVAL;
     hipError_t e;
     if (reg_path_ok(x, y, in_dtype, rows, rowlen, total, ch, hq, L, L, frac, acc_bits)) {
-        if (in_dtype == FIR_IN_U8) {
-            e = stage == FIR_OUT_U8_SAT
-                    ? launch_reg_taps<uint8_t, FIR_OUT_U8_SAT, 1, 1>(L, x, y, rows, total, rowlen, hq, frac, acc_bits, stream)
-                    : launch_reg_taps<uint8_t, FIR_OUT_I32, 1, 1>(L, x, y, rows, total, rowlen, hq, frac, acc_bits, stream);
-        } else if (ch == 1) {
-            e = stage == FIR_OUT_U8_SAT
-                    ? launch_reg_taps<int16_t, FIR_OUT_U8_SAT, 1, 1>(L, x, y, rows, total, rowlen, hq, frac, acc_bits, stream)
-                    : launch_reg_taps<int16_t, FIR_OUT_I32, 1, 1>(L, x, y, rows, total, rowlen, hq, frac, acc_bits, stream);
-        } else {
-            e = stage == FIR_OUT_U8_SAT
-                    ? launch_reg_taps<int16_t, FIR_OUT_U8_SAT, 2, 1>(L, x, y, rows, total, rowlen, hq, frac, acc_bits, stream)
-                    : launch_reg_taps<int16_t, FIR_OUT_I32, 2, 1>(L, x, y, rows, total, rowlen, hq, frac, acc_bits, stream);
-        }
+        e = launch_reg_one(in_dtype, stage, ch, L, x, y, rows, total, rowlen, hq, frac, acc_bits, stream);
     } else if (L >= (in_dtype == FIR_IN_I16 && stage == FIR_OUT_I32 ? kMfmaMinTapsI32 : kMfmaMinTaps) &&
                mfma_path_ok(x, y, in_dtype, rows, rowlen, total, ch, hq, L, frac, acc_bits)) {
         e = launch_fir1d_mfma(x, in_dtype, rows, rowlen, total, hq, L, frac, acc_bits, stage, y, stream);
@@ -280,29 +272,26 @@ int launch_fir1d_rows(const void* x, int in_dtype, int64_t rows, int64_t width, 
 }
 
 // u8 images: up to 4 filters per launch share one read of x.
-template <int STAGE>
-static hipError_t launch_multi_u8(int F, int L, const void* x, void* y, int64_t rows, int64_t total, int64_t rowlen,
-                                  const int32_t* hq, int frac, int acc_bits, hipStream_t s) {
-    switch (F) {
-        case 1: return launch_reg_taps<uint8_t, STAGE, 1, 1>(L, x, y, rows, total, rowlen, hq, frac, acc_bits, s);
-        case 2: return launch_reg_taps<uint8_t, STAGE, 1, 2>(L, x, y, rows, total, rowlen, hq, frac, acc_bits, s);
-        case 3: return launch_reg_taps<uint8_t, STAGE, 1, 3>(L, x, y, rows, total, rowlen, hq, frac, acc_bits, s);
-        case 4: return launch_reg_taps<uint8_t, STAGE, 1, 4>(L, x, y, rows, total, rowlen, hq, frac, acc_bits, s);
-        default: return hipErrorInvalidValue;
-    }
+static hipError_t launch_multi_u8(int stage, int F, int L, const void* x, void* y, int64_t rows, int64_t total,
+                                  int64_t rowlen, const int32_t* hq, int frac, int acc_bits, hipStream_t s) {
+    return with_stage(stage, [&](auto st) {
+        constexpr int STAGE = decltype(st)::value;
+        return with_int<1, 4>(F, hipErrorInvalidValue, [&](auto f) {
+            return launch_reg_taps<uint8_t, STAGE, 1, f>(L, x, y, rows, total, rowlen, hq, frac, acc_bits, s);
+        });
+    });
 }
 
 int launch_fir1d_rows_multi(const void* x, int in_dtype, int64_t rows, int64_t width, int ch, const int32_t* hq,
                             int L, int F, int frac, int acc_bits, int stage, void* y, hipStream_t stream,
                             std::string* err) {
-    if (F < 1) return *err = "filters must be >= 1", FIR_EINVAL;
-    int rc = check_common(in_dtype, rows, width, ch, hq, L, frac, acc_bits, stage, err);
+    int rc = check_fir1d(in_dtype, rows, width, ch, hq, L, F, frac, acc_bits, stage, err);
     if (rc) return rc;
     const int64_t rowlen = width * ch;
     const int64_t total = rows * rowlen;
     if (total == 0) return FIR_OK;
     if (!x || !y) return *err = "x and y must not be NULL", FIR_EINVAL;
-    const size_t osz = stage == FIR_OUT_I32 ? 4 : 1;
+    const size_t osz = out_size(stage);
     // u8 output planes start where the previous one ends, at any byte (the reference's 4499 x 2999
     // image: plane f at f * 13492501): the fused kernel's 16-byte stores then run unaligned, which
     // gfx950 performs in the unaligned-access mode ROCm sets for compute queues (byte-aligned store
@@ -316,10 +305,7 @@ int launch_fir1d_rows_multi(const void* x, int in_dtype, int64_t rows, int64_t w
         void* yf = (char*)y + (size_t)f0 * (size_t)total * osz;
         const int32_t* hf = hq + (size_t)f0 * L;
         if (fused) {
-            const hipError_t e =
-                stage == FIR_OUT_U8_SAT
-                    ? launch_multi_u8<FIR_OUT_U8_SAT>(nf, L, x, yf, rows, total, rowlen, hf, frac, acc_bits, stream)
-                    : launch_multi_u8<FIR_OUT_I32>(nf, L, x, yf, rows, total, rowlen, hf, frac, acc_bits, stream);
+            const hipError_t e = launch_multi_u8(stage, nf, L, x, yf, rows, total, rowlen, hf, frac, acc_bits, stream);
             if (e != hipSuccess) return *err = std::string("fir1d multi launch failed: ") + hipGetErrorString(e), FIR_EHIP;
         } else {
             rc = launch_fir1d_rows(x, in_dtype, rows, width, ch, hf, L, frac, acc_bits, stage, yf, stream, err);
@@ -330,12 +316,6 @@ int launch_fir1d_rows_multi(const void* x, int in_dtype, int64_t rows, int64_t w
     return FIR_OK;
 }
 
-template <int F>
-static hipError_t launch_batch_u8(int L, int n, const RegImage* im, const int32_t* hq, int frac, int acc_bits,
-                                  hipStream_t s) {
-    return launch_reg_batch_taps<uint8_t, FIR_OUT_U8_SAT, 1, F>(L, n, im, hq, frac, acc_bits, s);
-}
-
 int launch_fir1d_images_multi(int n, const void* const* xs, const int64_t* rows, const int64_t* widths, int in_dtype,
                               int ch, const int32_t* hq, int L, int F, int frac, int acc_bits, int stage,
                               void* const* planes, hipStream_t stream, std::string* err) {
@@ -344,7 +324,7 @@ int launch_fir1d_images_multi(int n, const void* const* xs, const int64_t* rows,
     if (!xs || !planes || !rows || !widths) return *err = "image arrays must not be NULL", FIR_EINVAL;
     if (F < 1) return *err = "filters must be >= 1", FIR_EINVAL;
     for (int i = 0; i < n; ++i) {  // the whole call is refused before anything runs
-        int rc = check_common(in_dtype, rows[i], widths[i], ch, hq, L, frac, acc_bits, stage, err);
+        int rc = check_fir1d(in_dtype, rows[i], widths[i], ch, hq, L, F, frac, acc_bits, stage, err);
         if (rc) return *err = "image " + std::to_string(i) + ": " + *err, rc;
         bool null = !xs[i];
         for (int f = 0; f < F; ++f) null |= !planes[(size_t)i * F + f];
@@ -386,13 +366,9 @@ int launch_fir1d_images_multi(int n, const void* const* xs, const int64_t* rows,
                 for (int f = 0; f < 4; ++f) im[j].y[f] = f < nf ? planes[(size_t)i * F + f0 + f] : nullptr;
             }
             const int32_t* hf = hq + (size_t)f0 * L;
-            hipError_t e;
-            switch (nf) {
-                case 1: e = launch_batch_u8<1>(L, nb, im, hf, frac, acc_bits, stream); break;
-                case 2: e = launch_batch_u8<2>(L, nb, im, hf, frac, acc_bits, stream); break;
-                case 3: e = launch_batch_u8<3>(L, nb, im, hf, frac, acc_bits, stream); break;
-                default: e = launch_batch_u8<4>(L, nb, im, hf, frac, acc_bits, stream); break;
-            }
+            const hipError_t e = with_int<1, 4>(nf, hipErrorInvalidValue, [&](auto f) {
+                return launch_reg_batch_taps<uint8_t, FIR_OUT_U8_SAT, 1, f>(L, nb, im, hf, frac, acc_bits, stream);
+            });
             if (e != hipSuccess) return *err = std::string("fir1d batch launch failed: ") + hipGetErrorString(e), FIR_EHIP;
         }
     }
@@ -406,26 +382,15 @@ int launch_fir1d_images_multi(int n, const void* const* xs, const int64_t* rows,
 int launch_fir1d_segment(const void* x, int in_dtype, int64_t n, int ch, const int32_t* hq, int L, int frac,
                          int acc_bits, int stage, const void* hl, const void* hr, void* y, hipStream_t stream,
                          std::string* err) {
-    int rc = check_common(in_dtype, 1, n, ch, hq, L, frac, acc_bits, stage, err);
+    int rc = check_fir1d(in_dtype, 1, n, ch, hq, L, 1, frac, acc_bits, stage, err);
     if (rc) return rc;
     const int64_t total = n * ch;
     if (total == 0) return FIR_OK;
     if (!x || !y) return *err = "x and y must not be NULL", FIR_EINVAL;
     if (total % reg_tile_samples(in_dtype == FIR_IN_U8) == 0 &&
         reg_path_ok(x, y, in_dtype, 1, total, total, ch, hq, L, L, frac, acc_bits)) {
-        hipError_t e;
-        if (in_dtype == FIR_IN_U8)
-            e = stage == FIR_OUT_U8_SAT
-                    ? launch_reg_taps<uint8_t, FIR_OUT_U8_SAT, 1, 1>(L, x, y, 1, total, total, hq, frac, acc_bits, stream, hl, hr)
-                    : launch_reg_taps<uint8_t, FIR_OUT_I32, 1, 1>(L, x, y, 1, total, total, hq, frac, acc_bits, stream, hl, hr);
-        else if (ch == 1)
-            e = stage == FIR_OUT_U8_SAT
-                    ? launch_reg_taps<int16_t, FIR_OUT_U8_SAT, 1, 1>(L, x, y, 1, total, total, hq, frac, acc_bits, stream, hl, hr)
-                    : launch_reg_taps<int16_t, FIR_OUT_I32, 1, 1>(L, x, y, 1, total, total, hq, frac, acc_bits, stream, hl, hr);
-        else
-            e = stage == FIR_OUT_U8_SAT
-                    ? launch_reg_taps<int16_t, FIR_OUT_U8_SAT, 2, 1>(L, x, y, 1, total, total, hq, frac, acc_bits, stream, hl, hr)
-                    : launch_reg_taps<int16_t, FIR_OUT_I32, 2, 1>(L, x, y, 1, total, total, hq, frac, acc_bits, stream, hl, hr);
+        const hipError_t e =
+            launch_reg_one(in_dtype, stage, ch, L, x, y, 1, total, total, hq, frac, acc_bits, stream, hl, hr);
         if (e != hipSuccess) return *err = std::string("fir1d segment launch failed: ") + hipGetErrorString(e), FIR_EHIP;
         return FIR_OK;
     }
@@ -437,7 +402,7 @@ int launch_fir1d_segment(const void* x, int in_dtype, int64_t n, int ch, const i
 int launch_fir1d_edges(const void* x, int in_dtype, int64_t n, int ch, const int32_t* hq, int L, int frac,
                        int acc_bits, int stage, const void* hl, const void* hr, void* y, hipStream_t stream,
                        std::string* err) {
-    int rc = check_common(in_dtype, 1, n, ch, hq, L, frac, acc_bits, stage, err);
+    int rc = check_fir1d(in_dtype, 1, n, ch, hq, L, 1, frac, acc_bits, stage, err);
     if (rc) return rc;
     const int64_t total = n * ch;
     if (total == 0) return FIR_OK;
@@ -453,14 +418,10 @@ int launch_fir1d_edges(const void* x, int in_dtype, int64_t n, int ch, const int
         if (!td) return FIR_ENOMEM;
         TableHold hold(td, stream);
         const bool wide = needs_wide(in_dtype, hq, L, acc_bits);
-        if (in_dtype == FIR_IN_U8)
-            e = stage == FIR_OUT_U8_SAT
-                    ? launch_edges<uint8_t, FIR_OUT_U8_SAT>(x, y, total, ch, hl, hr, td, L, hle, hre, frac, acc_bits, wide, stream)
-                    : launch_edges<uint8_t, FIR_OUT_I32>(x, y, total, ch, hl, hr, td, L, hle, hre, frac, acc_bits, wide, stream);
-        else
-            e = stage == FIR_OUT_U8_SAT
-                    ? launch_edges<int16_t, FIR_OUT_U8_SAT>(x, y, total, ch, hl, hr, td, L, hle, hre, frac, acc_bits, wide, stream)
-                    : launch_edges<int16_t, FIR_OUT_I32>(x, y, total, ch, hl, hr, td, L, hle, hre, frac, acc_bits, wide, stream);
+        e = with_io(in_dtype, stage, [&](auto t, auto st) {
+            return launch_edges<typename decltype(t)::type, st>(x, y, total, ch, hl, hr, td, L, hle, hre, frac, acc_bits,
+                                                                wide, stream);
+        });
     }
     if (e != hipSuccess) return *err = std::string("fir1d edge launch failed: ") + hipGetErrorString(e), FIR_EHIP;
     return FIR_OK;

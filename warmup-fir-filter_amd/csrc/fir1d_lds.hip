@@ -19,6 +19,7 @@
 #include <string>
 
 #include "fir_common.h"
+#include "fir_dispatch.h"
 #include "fir_launch.h"
 
 namespace fir {
@@ -225,11 +226,9 @@ bool lds_path_ok(const void* x, const void* y, int in_dtype, int64_t rows, int64
 hipError_t launch_fir1d_lds(const void* x, int in_dtype, int64_t rows, int64_t rowlen, int64_t total,
                             const int32_t* hq, int L, int frac, int acc_bits, int stage, void* y, hipStream_t s) {
     const int64_t rl = rows > 1 ? rowlen : 0;
-    if (in_dtype == FIR_IN_U8)
-        return stage == FIR_OUT_U8_SAT ? launch_lds_t<uint8_t, FIR_OUT_U8_SAT>(x, y, total, rl, hq, L, frac, acc_bits, s)
-                                       : launch_lds_t<uint8_t, FIR_OUT_I32>(x, y, total, rl, hq, L, frac, acc_bits, s);
-    return stage == FIR_OUT_U8_SAT ? launch_lds_t<int16_t, FIR_OUT_U8_SAT>(x, y, total, rl, hq, L, frac, acc_bits, s)
-                                   : launch_lds_t<int16_t, FIR_OUT_I32>(x, y, total, rl, hq, L, frac, acc_bits, s);
+    return with_io(in_dtype, stage, [&](auto t, auto st) {
+        return launch_lds_t<typename decltype(t)::type, st>(x, y, total, rl, hq, L, frac, acc_bits, s);
+    });
 }
 
 }  // namespace fir

@@ -30,6 +30,7 @@
 #include <vector>
 
 #include "fir_common.h"
+#include "fir_dispatch.h"
 #include "fir_launch.h"
 
 namespace fir {
@@ -1069,11 +1070,9 @@ bool mfma_path_ok(const void* x, const void* y, int in_dtype, int64_t rows, int6
 
 hipError_t launch_fir1d_mfma(const void* x, int in_dtype, int64_t rows, int64_t rowlen, int64_t total,
                              const int32_t* hq, int L, int frac, int acc_bits, int stage, void* y, hipStream_t s) {
-    if (in_dtype == FIR_IN_U8)
-        return stage == FIR_OUT_U8_SAT ? launch_mfma_t<uint8_t, FIR_OUT_U8_SAT>(x, y, rows, rowlen, total, hq, L, frac, acc_bits, s)
-                                       : launch_mfma_t<uint8_t, FIR_OUT_I32>(x, y, rows, rowlen, total, hq, L, frac, acc_bits, s);
-    return stage == FIR_OUT_U8_SAT ? launch_mfma_t<int16_t, FIR_OUT_U8_SAT>(x, y, rows, rowlen, total, hq, L, frac, acc_bits, s)
-                                   : launch_mfma_t<int16_t, FIR_OUT_I32>(x, y, rows, rowlen, total, hq, L, frac, acc_bits, s);
+    return with_io(in_dtype, stage, [&](auto t, auto st) {
+        return launch_mfma_t<typename decltype(t)::type, st>(x, y, rows, rowlen, total, hq, L, frac, acc_bits, s);
+    });
 }
 
 }  // namespace fir

@@ -8,6 +8,7 @@
 
 #include "fir1d_reg.h"
 #include "fir1d_reg_launch.h"
+#include "fir_dispatch.h"
 
 namespace fir {
 
@@ -193,31 +194,19 @@ static hipError_t launch_reg(const Go& go, const int32_t* hq, int frac, int acc_
 template <typename InT, int STAGE, int CH, int F>
 hipError_t launch_reg_taps(int L, const void* x, void* y, int64_t rows, int64_t total, int64_t rowlen,
                            const int32_t* hq, int frac, int acc_bits, hipStream_t s, const void* hl, const void* hr) {
-    switch (L) {
-        case 1: return launch_reg<InT, STAGE, 1, CH, F>(RegOne<InT, STAGE, 1, CH, F>{x, y, rows, total, rowlen, hq, frac, acc_bits, s, hl, hr}, hq, frac, acc_bits);
-        case 2: return launch_reg<InT, STAGE, 2, CH, F>(RegOne<InT, STAGE, 2, CH, F>{x, y, rows, total, rowlen, hq, frac, acc_bits, s, hl, hr}, hq, frac, acc_bits);
-        case 3: return launch_reg<InT, STAGE, 3, CH, F>(RegOne<InT, STAGE, 3, CH, F>{x, y, rows, total, rowlen, hq, frac, acc_bits, s, hl, hr}, hq, frac, acc_bits);
-        case 4: return launch_reg<InT, STAGE, 4, CH, F>(RegOne<InT, STAGE, 4, CH, F>{x, y, rows, total, rowlen, hq, frac, acc_bits, s, hl, hr}, hq, frac, acc_bits);
-        case 5: return launch_reg<InT, STAGE, 5, CH, F>(RegOne<InT, STAGE, 5, CH, F>{x, y, rows, total, rowlen, hq, frac, acc_bits, s, hl, hr}, hq, frac, acc_bits);
-        case 6: return launch_reg<InT, STAGE, 6, CH, F>(RegOne<InT, STAGE, 6, CH, F>{x, y, rows, total, rowlen, hq, frac, acc_bits, s, hl, hr}, hq, frac, acc_bits);
-        case 7: return launch_reg<InT, STAGE, 7, CH, F>(RegOne<InT, STAGE, 7, CH, F>{x, y, rows, total, rowlen, hq, frac, acc_bits, s, hl, hr}, hq, frac, acc_bits);
-        case 8: return launch_reg<InT, STAGE, 8, CH, F>(RegOne<InT, STAGE, 8, CH, F>{x, y, rows, total, rowlen, hq, frac, acc_bits, s, hl, hr}, hq, frac, acc_bits);
-        case 9: return launch_reg<InT, STAGE, 9, CH, F>(RegOne<InT, STAGE, 9, CH, F>{x, y, rows, total, rowlen, hq, frac, acc_bits, s, hl, hr}, hq, frac, acc_bits);
-        default: return hipErrorInvalidValue;
-    }
+    return with_int<1, 9>(L, hipErrorInvalidValue, [&](auto l) {
+        return launch_reg<InT, STAGE, l, CH, F>(
+            RegOne<InT, STAGE, l, CH, F>{x, y, rows, total, rowlen, hq, frac, acc_bits, s, hl, hr}, hq, frac, acc_bits);
+    });
 }
 
 template <typename InT, int STAGE, int CH, int F>
 hipError_t launch_reg_batch_taps(int L, int n, const RegImage* im, const int32_t* hq, int frac, int acc_bits,
                                  hipStream_t s) {
-    switch (L) {
-#define FIR_BATCH_L(l) \
-    case l: return launch_reg<InT, STAGE, l, CH, F>(RegMany<InT, STAGE, l, CH, F>{n, im, hq, frac, acc_bits, s}, hq, frac, acc_bits);
-        FIR_BATCH_L(1) FIR_BATCH_L(2) FIR_BATCH_L(3) FIR_BATCH_L(4) FIR_BATCH_L(5)
-        FIR_BATCH_L(6) FIR_BATCH_L(7) FIR_BATCH_L(8) FIR_BATCH_L(9)
-#undef FIR_BATCH_L
-        default: return hipErrorInvalidValue;
-    }
+    return with_int<1, 9>(L, hipErrorInvalidValue, [&](auto l) {
+        return launch_reg<InT, STAGE, l, CH, F>(RegMany<InT, STAGE, l, CH, F>{n, im, hq, frac, acc_bits, s}, hq, frac,
+                                                acc_bits);
+    });
 }
 
 }  // namespace fir

@@ -18,6 +18,7 @@
 #include "fir2d_pk16.h"
 #include "fir2d_reg.h"
 #include "fir_common.h"
+#include "fir_dispatch.h"
 #include "fir_launch.h"
 
 namespace fir {
@@ -276,8 +277,8 @@ static bool sep2d_register_form(const int32_t* hq, int R, int C) {
     return R > 1 && C > 1 && rank1_factor(hq, R, C, col, row);
 }
 
-int launch_fir2d(const uint8_t* x, int64_t frames, int64_t H, int64_t W, const int32_t* hq, int R, int C, int frac,
-                 int acc_bits, int stage, void* y, hipStream_t stream, std::string* err) {
+int check_fir2d(int64_t frames, int64_t H, int64_t W, const int32_t* hq, int R, int C, int frac, int acc_bits, int stage,
+                std::string* err) {
     if (stage != FIR_OUT_U8_SAT && stage != FIR_OUT_I32) return *err = "out_stage must be FIR_OUT_U8_SAT or FIR_OUT_I32", FIR_EINVAL;
     if (H < 0 || W < 0 || frames < 0) return *err = "frames, height and width must be >= 0", FIR_EINVAL;
     if (frames > 65535) return *err = "frames must be <= 65535 per call", FIR_EINVAL;
@@ -285,6 +286,12 @@ int launch_fir2d(const uint8_t* x, int64_t frames, int64_t H, int64_t W, const i
     if (R < 1 || C < 1 || (int64_t)R * C > FIR_MAX_TAPS)
         return *err = "tap_rows*tap_cols must be in [1, " + std::to_string(FIR_MAX_TAPS) + "]", FIR_EINVAL;
     if (frac < 1 || acc_bits < 1) return *err = "frac_bits and acc_bits must be >= 1", FIR_EINVAL;
+    return FIR_OK;
+}
+
+int launch_fir2d(const uint8_t* x, int64_t frames, int64_t H, int64_t W, const int32_t* hq, int R, int C, int frac,
+                 int acc_bits, int stage, void* y, hipStream_t stream, std::string* err) {
+    if (const int rc = check_fir2d(frames, H, W, hq, R, C, frac, acc_bits, stage, err)) return rc;
     const int64_t ntaps = (int64_t)R * C;
     bool wide = false;  // a no-wrap call whose exact sum could reach 2^63: 128-bit sums
     if (acc_bits >= 64) {
@@ -312,26 +319,24 @@ int launch_fir2d(const uint8_t* x, int64_t frames, int64_t H, int64_t W, const i
     if (e != hipErrorNotSupported) {
         // launched (or failed to launch) on the matrix cores
     } else if (fast) {
-        e = stage == FIR_OUT_U8_SAT ? launch2d_reg_shape<FIR_OUT_U8_SAT>(R, C, x, y, frames, H, W, hq, frac, acc_bits, stream)
-                                    : launch2d_reg_shape<FIR_OUT_I32>(R, C, x, y, frames, H, W, hq, frac, acc_bits, stream);
+        e = with_stage(stage, [&](auto st) {
+            return launch2d_reg_shape<st>(R, C, x, y, frames, H, W, hq, frac, acc_bits, stream);
+        });
     } else {
         if ((W + kBlock - 1) / kBlock >= ((int64_t)1 << 31)) return *err = "width too large", FIR_EINVAL;
         const int32_t* td = (const int32_t*)device_table(hq, sizeof(int32_t) * (size_t)ntaps, err);
         if (!td) return FIR_ENOMEM;
         TableHold hold(td, stream);
         dim3 grid((unsigned)((W + kBlock - 1) / kBlock), (unsigned)std::min<int64_t>(H, 65535), (unsigned)frames);
-        if (stage == FIR_OUT_U8_SAT && wide)
-            hipLaunchKernelGGL((fir2d_generic_kernel<FIR_OUT_U8_SAT, true>), grid, dim3(kBlock), 0, stream, x, (uint8_t*)y,
-                               H, W, td, R, C, frac, acc_bits);
-        else if (stage == FIR_OUT_U8_SAT)
-            hipLaunchKernelGGL((fir2d_generic_kernel<FIR_OUT_U8_SAT, false>), grid, dim3(kBlock), 0, stream, x, (uint8_t*)y,
-                               H, W, td, R, C, frac, acc_bits);
-        else if (wide)
-            hipLaunchKernelGGL((fir2d_generic_kernel<FIR_OUT_I32, true>), grid, dim3(kBlock), 0, stream, x, (int32_t*)y,
-                               H, W, td, R, C, frac, acc_bits);
-        else
-            hipLaunchKernelGGL((fir2d_generic_kernel<FIR_OUT_I32, false>), grid, dim3(kBlock), 0, stream, x, (int32_t*)y,
-                               H, W, td, R, C, frac, acc_bits);
+        with_stage(stage, [&](auto st) {
+            using OutT = typename OutTraits<st>::T;
+            if (wide)
+                hipLaunchKernelGGL((fir2d_generic_kernel<st, true>), grid, dim3(kBlock), 0, stream, x, (OutT*)y, H, W, td,
+                                   R, C, frac, acc_bits);
+            else
+                hipLaunchKernelGGL((fir2d_generic_kernel<st, false>), grid, dim3(kBlock), 0, stream, x, (OutT*)y, H, W, td,
+                                   R, C, frac, acc_bits);
+        });
         e = hipGetLastError();
     }
     if (e != hipSuccess) return *err = std::string("fir2d launch failed: ") + hipGetErrorString(e), FIR_EHIP;

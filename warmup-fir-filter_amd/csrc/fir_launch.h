@@ -8,6 +8,8 @@
 #include <string>
 #include <vector>
 
+#include "fir_hip.h"
+
 namespace fir {
 
 // Device copies of host tables (long tap sets, matrix-core tap fragments) on the current device
@@ -40,6 +42,22 @@ struct TableHold {  // one launch's hold: released (its use recorded on `s`) whe
     TableHold& operator=(const TableHold&) = delete;
     ~TableHold() { table_release(p, s); }
 };
+
+// The check_* functions are the structural checks each launcher runs first, on their own: what a
+// host entry refuses before it needs a device (an empty problem passes zero sizes).  fir_status
+// and *err, as the launchers.
+int check_fir1d(int in_dtype, int64_t rows, int64_t width, int ch, const int32_t* hq, int L, int F, int frac,
+                int acc_bits, int stage, std::string* err);
+int check_fir1d_ideal(int64_t rows, int64_t width, const double* h, int L, std::string* err);
+int check_fir2d(int64_t frames, int64_t height, int64_t width, const int32_t* hq, int tap_rows, int tap_cols, int frac,
+                int acc_bits, int stage, std::string* err);
+int check_fir2d_ideal(int64_t frames, int64_t height, int64_t width, const double* h, int tap_rows, int tap_cols,
+                      std::string* err);
+int check_restore_u8(int64_t n, int policy, std::string* err);
+
+// bytes per sample of a (checked) fir_in_dtype / fir_out_stage
+inline size_t in_size(int in_dtype) { return in_dtype == FIR_IN_I16 ? 2 : 1; }
+inline size_t out_size(int stage) { return stage == FIR_OUT_I32 ? 4 : 1; }
 
 // Enqueue the row-wise 1-D fixed FIR on `stream`; device pointers.  Returns fir_status.
 int launch_fir1d_rows(const void* x, int in_dtype, int64_t rows, int64_t width, int ch, const int32_t* hq, int L,
@@ -102,9 +120,6 @@ int launch_fir1d_ideal(const uint8_t* x, int64_t rows, int64_t width, const doub
                        hipStream_t stream, std::string* err);
 
 // float64 ideal model of the 2-D FIR over `frames` uint8 frames stored back to back (ideal2d.hip).
-// check_fir2d_ideal: the structural checks alone (what a host entry refuses before it needs a device).
-int check_fir2d_ideal(int64_t frames, int64_t height, int64_t width, const double* h, int tap_rows, int tap_cols,
-                      std::string* err);
 int launch_fir2d_ideal(const uint8_t* x, int64_t frames, int64_t height, int64_t width, const double* h, int tap_rows,
                        int tap_cols, double* y, hipStream_t stream, std::string* err);
 

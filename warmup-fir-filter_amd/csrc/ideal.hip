@@ -14,6 +14,7 @@
 #include <string>
 
 #include "fir_common.h"
+#include "fir_dispatch.h"
 #include "fir_launch.h"
 #include "ideal_reg.h"
 
@@ -93,11 +94,16 @@ static hipError_t launch_ideal_reg(const uint8_t* x, double* y, int64_t rows, in
     return hipGetLastError();
 }
 
-int launch_fir1d_ideal(const uint8_t* x, int64_t rows, int64_t width, const double* h, int L, double* y,
-                       hipStream_t stream, std::string* err) {
+int check_fir1d_ideal(int64_t rows, int64_t width, const double* h, int L, std::string* err) {
     if (rows < 0 || width < 0) return *err = "rows and width must be >= 0", FIR_EINVAL;
     if (!h) return *err = "h must not be NULL", FIR_EINVAL;
     if (L < 1 || L > FIR_MAX_TAPS) return *err = "taps must be in [1, " + std::to_string(FIR_MAX_TAPS) + "]", FIR_EINVAL;
+    return FIR_OK;
+}
+
+int launch_fir1d_ideal(const uint8_t* x, int64_t rows, int64_t width, const double* h, int L, double* y,
+                       hipStream_t stream, std::string* err) {
+    if (const int rc = check_fir1d_ideal(rows, width, h, L, err)) return rc;
     const int64_t total = rows * width;
     if (total == 0) return FIR_OK;
     if (!x || !y) return *err = "x and y must not be NULL", FIR_EINVAL;
@@ -105,18 +111,9 @@ int launch_fir1d_ideal(const uint8_t* x, int64_t rows, int64_t width, const doub
                      (rows == 1 || (width >= 4 * kIdealNV + L - 1 && total < ((int64_t)1 << 32))) &&
                      (total + 4 * kIdealNV - 1) / (4 * kIdealNV) / kBlock < ((int64_t)1 << 31);
     if (reg) {
-        hipError_t e = hipErrorInvalidValue;
-        switch (L) {
-            case 1: e = launch_ideal_reg<1>(x, y, rows, width, h, stream); break;
-            case 2: e = launch_ideal_reg<2>(x, y, rows, width, h, stream); break;
-            case 3: e = launch_ideal_reg<3>(x, y, rows, width, h, stream); break;
-            case 4: e = launch_ideal_reg<4>(x, y, rows, width, h, stream); break;
-            case 5: e = launch_ideal_reg<5>(x, y, rows, width, h, stream); break;
-            case 6: e = launch_ideal_reg<6>(x, y, rows, width, h, stream); break;
-            case 7: e = launch_ideal_reg<7>(x, y, rows, width, h, stream); break;
-            case 8: e = launch_ideal_reg<8>(x, y, rows, width, h, stream); break;
-            case 9: e = launch_ideal_reg<9>(x, y, rows, width, h, stream); break;
-        }
+        const hipError_t e = with_int<1, 9>(L, hipErrorInvalidValue, [&](auto l) {
+            return launch_ideal_reg<l>(x, y, rows, width, h, stream);
+        });
         if (e != hipSuccess) return *err = std::string("ideal launch failed: ") + hipGetErrorString(e), FIR_EHIP;
         return FIR_OK;
     }

@@ -30,6 +30,7 @@
 #include <string>
 
 #include "fir_common.h"
+#include "fir_dispatch.h"
 #include "fir_launch.h"
 
 namespace fir {
@@ -216,19 +217,6 @@ static hipError_t launch_ideal2d_reg(const uint8_t* x, double* y, int64_t frames
     return hipGetLastError();
 }
 
-template <int R>
-static hipError_t launch_ideal2d_reg_cols(int C, const uint8_t* x, double* y, int64_t frames, int64_t H, int64_t W,
-                                          const double* h, hipStream_t s) {
-    switch (C) {
-        case 1: return launch_ideal2d_reg<R, 1>(x, y, frames, H, W, h, s);
-        case 2: return launch_ideal2d_reg<R, 2>(x, y, frames, H, W, h, s);
-        case 3: return launch_ideal2d_reg<R, 3>(x, y, frames, H, W, h, s);
-        case 4: return launch_ideal2d_reg<R, 4>(x, y, frames, H, W, h, s);
-        case 5: return launch_ideal2d_reg<R, 5>(x, y, frames, H, W, h, s);
-    }
-    return hipErrorInvalidValue;
-}
-
 int check_fir2d_ideal(int64_t frames, int64_t H, int64_t W, const double* h, int R, int C, std::string* err) {
     if (H < 0 || W < 0 || frames < 0) return *err = "frames, height and width must be >= 0", FIR_EINVAL;
     if (frames > 65535) return *err = "frames must be <= 65535 per call", FIR_EINVAL;
@@ -250,13 +238,12 @@ int launch_fir2d_ideal(const uint8_t* x, int64_t frames, int64_t H, int64_t W, c
                      (H + 65534) / 65535 < ((int64_t)1 << 30);
     hipError_t e = hipErrorInvalidValue;
     if (reg) {
-        switch (R) {
-            case 1: e = launch_ideal2d_reg_cols<1>(C, x, y, frames, H, W, h, stream); break;
-            case 2: e = launch_ideal2d_reg_cols<2>(C, x, y, frames, H, W, h, stream); break;
-            case 3: e = launch_ideal2d_reg_cols<3>(C, x, y, frames, H, W, h, stream); break;
-            case 4: e = launch_ideal2d_reg_cols<4>(C, x, y, frames, H, W, h, stream); break;
-            case 5: e = launch_ideal2d_reg_cols<5>(C, x, y, frames, H, W, h, stream); break;
-        }
+        e = with_int<1, kIdeal2dMaxRC>(R, hipErrorInvalidValue, [&](auto r) {
+            constexpr int TR = decltype(r)::value;
+            return with_int<1, kIdeal2dMaxRC>(C, hipErrorInvalidValue, [&](auto c) {
+                return launch_ideal2d_reg<TR, c>(x, y, frames, H, W, h, stream);
+            });
+        });
     } else {
         if ((W + kBlock - 1) / kBlock >= ((int64_t)1 << 31)) return *err = "width too large", FIR_EINVAL;
         const double* td = (const double*)device_table(h, sizeof(double) * (size_t)R * (size_t)C, err);

@@ -149,11 +149,16 @@ __global__ __launch_bounds__(kBlock) void restore_params_kernel(const double* __
 
 size_t restore_work_bytes() { return 256 + (size_t)kRestoreBlocks * 2 * sizeof(double); }
 
-int launch_restore_u8(const double* a, int64_t n, int policy, uint8_t* out, void* work, hipStream_t stream,
-                      std::string* err) {
+int check_restore_u8(int64_t n, int policy, std::string* err) {
     if (n < 0) return *err = "n must be >= 0", FIR_EINVAL;
     if (policy != FIR_RESTORE_CLIP && policy != FIR_RESTORE_NORMALIZE)
         return *err = "policy must be FIR_RESTORE_CLIP or FIR_RESTORE_NORMALIZE", FIR_EINVAL;
+    return FIR_OK;
+}
+
+int launch_restore_u8(const double* a, int64_t n, int policy, uint8_t* out, void* work, hipStream_t stream,
+                      std::string* err) {
+    if (const int rc = check_restore_u8(n, policy, err)) return rc;
     if (n == 0) return FIR_OK;
     if (!a || !out) return *err = "a and out must not be NULL", FIR_EINVAL;
     if ((uintptr_t)a % 16 || (uintptr_t)out % 16) return *err = "a and out must be 16-byte aligned", FIR_EINVAL;
