@@ -526,7 +526,7 @@ def test_host_entry_chunked_overlap(shape, dtype, channels, taps):
         assert np.array_equal(buf, ref)
 
 
-@pytest.mark.parametrize("c", [1365, 1366, 1370, 1371, 4095])
+@pytest.mark.parametrize("c", [1365, 1366, 1368, 1369, 1370, 1371, 4095])
 def test_bank_noclamp_stage_boundary(c):
     """A v_dot2-form filter whose biased sum provably stays in [0, 256 * 2^frac) runs its u8 stage
     as a shift alone (fir1d_reg.h plan_u8_noclamp): moving averages c * [1, 1, 1] on both sides of
