@@ -43,6 +43,8 @@
  *                         spread over several devices of this process (rows split, or a long
  *                         row split into segments with their halos); the reference has no
  *                         multi-device form.
+ *   fir_decim_rows[_dev]  none: the reference has no decimating form; fir1d_fixed_rows followed by
+ *                         y[..., phase::decim], computed in one pass that writes only what is kept.
  *   fir_restore_u8[_dev]  fir_1d/sim/vector/restore_images.py:51-64 (_to_u8_clip,
  *                         _to_u8_normalized), the array half of the restore stage.
  *
@@ -103,6 +105,38 @@ int fir1d_fixed_rows(const void* x, int in_dtype, int64_t rows, int64_t width, i
 int fir1d_fixed_rows_dev(const void* x_dev, int in_dtype, int64_t rows, int64_t width,
                          int channels, const int32_t* hq, int taps, int frac_bits, int acc_bits,
                          int out_stage, void* y_dev, void* stream);
+
+/* ---- decimating 1-D fixed-point FIR: filter and keep every decim-th output frame ------
+ * For decim = D >= 1 and 0 <= phase < D:
+ *
+ *   out_width  = width > phase ? (width - phase + D - 1) / D : 0
+ *   y[r, m, c] = y_full[r, m*D + phase, c]        m in [0, out_width), c in [0, channels)
+ *
+ * y_full is exactly what fir1d_fixed_rows gives for the same arguments: the same centre rule
+ * (taps/2), zero padding at each row's ends, wrap to acc_bits, round-half-up by frac_bits and the
+ * u8-sat or int32 stage, with exact sums for acc_bits >= 64 (128-bit where the sum could pass
+ * 2^63).  With channels > 1 decimation counts frames, not interleaved values.  y is C-contiguous,
+ * rows x out_width x channels, uint8 (FIR_OUT_U8_SAT) or int32 (FIR_OUT_I32).  D = 1 is the
+ * full-rate result.  Empty problems (rows, width or out_width equal to 0, phase >= width included)
+ * are no-ops returning FIR_OK.  Skipped samples may still be read; they never influence a kept
+ * output other than through the sum above.
+ * Checks, in this order: those of fir1d_fixed_rows_dev with their texts, "decim must be >= 1",
+ * "phase must be in [0, decim)", the sizes, NULL x or y (only when the problem is not empty), then
+ * the device lookup of the host form.
+ * fir_decim_out_width: out_width, or -1 for decim < 1, phase outside [0, decim) or width < 0.
+ * fir_decim_rows: host pointers, synchronous on `device`.  fir_decim_rows_dev: device pointers,
+ * enqueued on `stream`, never synchronises; with 2 <= decim <= 16, taps <= 128 within int16,
+ * acc_bits <= 32, frac_bits <= 31, u8 of one channel or int16 of one or two, x 16-byte aligned
+ * (u8: 8) and one row or rows of a multiple of 8 samples it allocates nothing and can be captured
+ * in a hipGraph (every other call reads its taps from a cached device table, whose first use
+ * cannot be captured).  Added without an ABI number change (additive, as fir2d_ideal*). */
+int64_t fir_decim_out_width(int64_t width, int decim, int phase);
+int fir_decim_rows(const void* x, int in_dtype, int64_t rows, int64_t width, int channels,
+                   const int32_t* hq, int taps, int decim, int phase, int frac_bits, int acc_bits,
+                   int out_stage, void* y, int device);
+int fir_decim_rows_dev(const void* x_dev, int in_dtype, int64_t rows, int64_t width, int channels,
+                       const int32_t* hq, int taps, int decim, int phase, int frac_bits, int acc_bits,
+                       int out_stage, void* y_dev, void* stream);
 
 /* F filters of `taps` taps each over the same x: hq is F x taps (row-major), y holds F
  * consecutive output planes shaped like x (plane f at y + f * rows*width*channels elements).

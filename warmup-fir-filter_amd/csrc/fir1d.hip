@@ -156,7 +156,7 @@ __global__ __launch_bounds__(kBlock) void fir1d_edges_kernel(const InT* __restri
 // A no-wrap call (acc_bits >= 64) whose exact sum could reach 2^63: the 128-bit generic kernels
 // (the reference's sum is an unbounded Python int, fir_1d_fixed_ref.py:94-115).  A wrap to
 // acc_bits < 64 is exact mod 2^64, and |sum| < 2^63 is exact in 64 bits.
-static bool needs_wide(int in_dtype, const int32_t* hq, int L, int acc_bits) {
+bool needs_wide(int in_dtype, const int32_t* hq, int L, int acc_bits) {
     if (acc_bits < 64) return false;
     unsigned __int128 habs = 0;
     for (int k = 0; k < L; ++k) habs += (unsigned __int128)(hq[k] < 0 ? -(int64_t)hq[k] : (int64_t)hq[k]);

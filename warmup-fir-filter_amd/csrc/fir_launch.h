@@ -76,6 +76,26 @@ bool lds_path_ok(const void* x, const void* y, int in_dtype, int64_t rows, int64
 hipError_t launch_fir1d_lds(const void* x, int in_dtype, int64_t rows, int64_t rowlen, int64_t total,
                             const int32_t* hq, int L, int frac, int acc_bits, int stage, void* y, hipStream_t s);
 
+// A no-wrap call (acc_bits >= 64) whose exact sum could reach 2^63: the generic kernels then sum
+// in 128 bits (fir1d.hip).
+bool needs_wide(int in_dtype, const int32_t* hq, int L, int acc_bits);
+
+// The decimating row-wise FIR (fir1d_decim.hip): y[r, m, c] = y_full[r, m * decim + phase, c] with
+// y_full what launch_fir1d_rows gives, rows x decim_out_width x ch outputs.  decim_out_width: -1
+// for a bad decim / phase / width.  check_fir1d_decim: check_fir1d's checks, then decim, phase
+// and the sizes; *out_width on success.  decim_path_ok: the LDS polyphase v_dot2 kernel applies
+// (2 <= decim <= 16, up to 128 int16 taps, acc_bits <= 32, frac <= 31, u8 of one channel or
+// int16 of one or two, x aligned as lds_path_ok asks, one row or rows of a multiple of 8
+// samples); every other call runs the generic one-output-per-thread kernel.
+int64_t decim_out_width(int64_t width, int decim, int phase);
+int check_fir1d_decim(int in_dtype, int64_t rows, int64_t width, int ch, const int32_t* hq, int L, int decim,
+                      int phase, int frac, int acc_bits, int stage, int64_t* out_width, std::string* err);
+bool decim_path_ok(const void* x, int in_dtype, int64_t rows, int64_t width, int ch, const int32_t* hq, int L,
+                   int decim, int frac, int acc_bits, int64_t out_width);
+int launch_fir1d_decim(const void* x, int in_dtype, int64_t rows, int64_t width, int ch, const int32_t* hq, int L,
+                       int decim, int phase, int frac, int acc_bits, int stage, void* y, hipStream_t stream,
+                       std::string* err);
+
 // F filters of L taps (hq row-major F x L) over the same x; y = F consecutive output planes.
 int launch_fir1d_rows_multi(const void* x, int in_dtype, int64_t rows, int64_t width, int ch, const int32_t* hq,
                             int L, int F, int frac, int acc_bits, int stage, void* y, hipStream_t stream,

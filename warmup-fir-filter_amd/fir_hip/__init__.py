@@ -6,7 +6,7 @@ library is missing, no gfx950 device is present, or a HIP call fails.  There is 
 CPU fallback: the product path fails loudly rather than computing elsewhere.
 
 Host-array entry points (NumPy in, NumPy out, synchronous):
-    fir1d_fixed_rows, fir1d_fixed_rows_multi, fir1d_fixed_rows_sharded, fir2d_fixed,
+    fir1d_fixed_rows, fir1d_fixed_rows_decim, fir1d_fixed_rows_multi, fir1d_fixed_rows_sharded, fir2d_fixed,
     fir2d_ideal, fir1d_ideal_rows, compare_metrics, restore_u8, and the stage drivers' image batches
     fir1d_fixed_images_multi / fir1d_ideal_images_multi (page-locked staging: host_empty)
 Device entry points (torch tensors on a HIP device, enqueued on the current stream):
@@ -27,7 +27,7 @@ __all__ = [
     "OUT_U8_SAT", "OUT_I32", "RESTORE_CLIP", "RESTORE_NORMALIZE", "MAX_TAPS", "EXPORTS", "ipc_export", "ipc_import",
     "ipc_close", "peek", "IPC_HANDLE_BYTES", "device_bus_id", "peer_access", "peer_atomics", "halo_mailbox_bytes",
     "GATE_TIMEOUT", "GATE_LAYOUT", "build_id", "parse_devices", "METRIC_DTYPES", "fir1d_fixed_images_multi",
-    "fir1d_ideal_images_multi", "host_empty", "TIMING_KEYS",
+    "fir1d_ideal_images_multi", "host_empty", "TIMING_KEYS", "decim_out_width", "fir1d_fixed_rows_decim",
 ]
 
 IN_U8, IN_I16 = 0, 1
@@ -60,6 +60,9 @@ EXPORTS = {
     "fir_device_count": (_i32, [ctypes.POINTER(_i32)]),
     "fir1d_fixed_rows": (_i32, [_vp, _i32, _i64, _i64, _i32, _vp, _i32, _i32, _i32, _i32, _vp, _i32]),
     "fir1d_fixed_rows_dev": (_i32, [_vp, _i32, _i64, _i64, _i32, _vp, _i32, _i32, _i32, _i32, _vp, _vp]),
+    "fir_decim_out_width": (_i64, [_i64, _i32, _i32]),
+    "fir_decim_rows": (_i32, [_vp, _i32, _i64, _i64, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _i32]),
+    "fir_decim_rows_dev": (_i32, [_vp, _i32, _i64, _i64, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
     "fir1d_fixed_rows_multi": (_i32, [_vp, _i32, _i64, _i64, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _i32]),
     "fir1d_fixed_rows_multi_dev": (_i32, [_vp, _i32, _i64, _i64, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
     "fir1d_fixed_images_multi_dev": (_i32, [_i32, _vp, _vp, _vp, _i32, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _vp,
@@ -298,6 +301,48 @@ def fir1d_fixed_rows(x: np.ndarray, hq, frac_bits: int = 12, acc_bits: int = 32,
     _check(lib().fir1d_fixed_rows(_ptr(x), in_dtype, rows, rowlen // channels, channels, _ptr(h), h.size,
                                   int(frac_bits), int(acc_bits), int(out_stage), _ptr(y), int(device)),
            "fir1d_fixed_rows")
+    return y
+
+
+def decim_out_width(width: int, decim: int, phase: int = 0) -> int:
+    """Frames a row of ``width`` frames keeps under ``y[phase::decim]`` (fir_decim_out_width);
+    FirHipError for decim < 1, a phase outside [0, decim) or a negative width.  Needs no library."""
+    width, decim, phase = int(width), int(decim), int(phase)
+    if decim < 1:
+        raise FirHipError("decim must be >= 1")
+    if not 0 <= phase < decim:
+        raise FirHipError("phase must be in [0, decim)")
+    if width < 0:
+        raise FirHipError("width must be >= 0")
+    return (width - phase + decim - 1) // decim if width > phase else 0
+
+
+def fir1d_fixed_rows_decim(x: np.ndarray, hq, decim: int, phase: int = 0, frac_bits: int = 12, acc_bits: int = 32,
+                           out_stage: int = OUT_U8_SAT, channels: int = 1, device: int = 0,
+                           out: np.ndarray | None = None) -> np.ndarray:
+    """fir1d_fixed_rows that keeps every ``decim``-th output frame, from frame ``phase`` of each
+    row: the value of ``fir1d_fixed_rows(x, ...)`` viewed as (..., width, channels)``[..., phase::decim, :]``
+    computed in one pass that writes only the kept frames.  Returns x's leading axes with a last
+    axis of decim_out_width(width, decim, phase) * channels values."""
+    x = np.ascontiguousarray(x)
+    if x.dtype == np.uint8:
+        in_dtype = IN_U8
+    elif x.dtype == np.int16:
+        in_dtype = IN_I16
+    else:
+        raise FirHipError(f"x dtype must be uint8 or int16, got {x.dtype}")
+    h = _taps_i32(hq)
+    if x.ndim == 0:
+        x = x.reshape(1)
+    rowlen = x.shape[-1]
+    rows = x.size // rowlen if rowlen else 0
+    if channels < 1 or rowlen % channels:
+        raise FirHipError("row length must be a multiple of channels")
+    ow = decim_out_width(rowlen // channels, decim, phase)
+    y = _out_buf(out, x.shape[:-1] + (ow * channels,), np.uint8 if out_stage == OUT_U8_SAT else np.int32, x)
+    _check(lib().fir_decim_rows(_ptr(x), in_dtype, rows, rowlen // channels, channels, _ptr(h), h.size, int(decim),
+                                int(phase), int(frac_bits), int(acc_bits), int(out_stage), _ptr(y), int(device)),
+           "fir_decim_rows")
     return y
 
 

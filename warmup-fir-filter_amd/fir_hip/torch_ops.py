@@ -12,7 +12,7 @@ import numpy as np
 import torch
 
 from . import (IN_I16, IN_U8, OUT_I32, OUT_U8_SAT, RESTORE_CLIP, RESTORE_NORMALIZE, FirHipError, _check, _taps2_f64,
-               _taps_i32, lib)
+               _taps_i32, decim_out_width, lib)
 
 _IN = {torch.uint8: IN_U8, torch.int16: IN_I16}
 _OUT_DTYPE = {OUT_U8_SAT: torch.uint8, OUT_I32: torch.int32}
@@ -68,6 +68,33 @@ def fir1d_fixed_rows_dev(x: torch.Tensor, hq, frac_bits: int = 12, acc_bits: int
                                       channels, t.ptr, t.n, int(frac_bits), int(acc_bits), int(out_stage),
                                       ctypes.c_void_p(out.data_ptr()), _stream_ptr(x, stream)),
            "fir1d_fixed_rows_dev")
+    return out
+
+
+def fir1d_fixed_rows_decim_dev(x: torch.Tensor, hq, decim: int, phase: int = 0, frac_bits: int = 12,
+                               acc_bits: int = 32, out_stage: int = OUT_I32, channels: int = 1,
+                               out: torch.Tensor | None = None, stream=None) -> torch.Tensor:
+    """fir1d_fixed_rows_dev that keeps every ``decim``-th output frame from frame ``phase`` of each
+    row (fir_decim_rows_dev): x's leading axes with a last axis of decim_out_width(width, decim,
+    phase) * channels values.  One pass: x is read once and only the kept frames are written."""
+    _check_dev(x, "x")
+    if x.dtype not in _IN:
+        raise FirHipError(f"x dtype must be uint8 or int16, got {x.dtype}")
+    t = _taps(hq)
+    rowlen = x.shape[-1] if x.dim() else 1
+    rows = x.numel() // rowlen if rowlen else 0
+    if channels < 1 or rowlen % channels:
+        raise FirHipError("row length must be a multiple of channels")
+    ow = decim_out_width(rowlen // channels, decim, phase)
+    shape = tuple(x.shape[:-1]) + (ow * channels,)
+    if out is None:
+        out = torch.empty(shape, dtype=_OUT_DTYPE[out_stage], device=x.device)
+    _check_dev(out, "out")
+    if tuple(out.shape) != shape or out.dtype != _OUT_DTYPE[out_stage]:
+        raise FirHipError(f"out must be {_OUT_DTYPE[out_stage]} of shape {shape}")
+    _check(lib().fir_decim_rows_dev(ctypes.c_void_p(x.data_ptr()), _IN[x.dtype], rows, rowlen // channels, channels,
+                                    t.ptr, t.n, int(decim), int(phase), int(frac_bits), int(acc_bits), int(out_stage),
+                                    ctypes.c_void_p(out.data_ptr()), _stream_ptr(x, stream)), "fir_decim_rows_dev")
     return out
 
 
