@@ -101,7 +101,8 @@ int fir1d_fixed_rows(const void* x, int in_dtype, int64_t rows, int64_t width, i
                      void* y, int device);
 
 /* Device-pointer form: enqueued on `stream` (hipStream_t; NULL = default stream of the
- * current device); returns after the launch, not after completion. */
+ * current device); returns after the launch, not after completion.  No `_dev` entry detects an
+ * output or work buffer that overlaps an input: the caller keeps them apart (nothing runs in place). */
 int fir1d_fixed_rows_dev(const void* x_dev, int in_dtype, int64_t rows, int64_t width,
                          int channels, const int32_t* hq, int taps, int frac_bits, int acc_bits,
                          int out_stage, void* y_dev, void* stream);
