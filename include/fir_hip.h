@@ -45,6 +45,9 @@
  *                         multi-device form.
  *   fir_decim_rows[_dev]  none: the reference has no decimating form; fir1d_fixed_rows followed by
  *                         y[..., phase::decim], computed in one pass that writes only what is kept.
+ *   fir_interp_rows[_dev] none: the reference has no interpolating form; fir1d_fixed_rows of the
+ *                         signal with up-1 zero frames after every frame, computed in polyphase
+ *                         form from x itself.
  *   fir_restore_u8[_dev]  fir_1d/sim/vector/restore_images.py:51-64 (_to_u8_clip,
  *                         _to_u8_normalized), the array half of the restore stage.
  *
@@ -138,6 +141,44 @@ int fir_decim_rows(const void* x, int in_dtype, int64_t rows, int64_t width, int
 int fir_decim_rows_dev(const void* x_dev, int in_dtype, int64_t rows, int64_t width, int channels,
                        const int32_t* hq, int taps, int decim, int phase, int frac_bits, int acc_bits,
                        int out_stage, void* y_dev, void* stream);
+
+/* ---- interpolating 1-D fixed-point FIR: zero-stuff by `up`, then filter ------------------
+ * For up = U >= 1:
+ *
+ *   out_width      = width * U
+ *   xu[r, i*U, c]  = x[r, i, c], every other frame of xu is 0     (rows x out_width x channels)
+ *   y              = what fir1d_fixed_rows gives for xu with the same hq, frac_bits, acc_bits,
+ *                    out_stage and channels
+ *
+ * so the same centre rule (taps/2), zero padding at each row's ends, wrap to acc_bits,
+ * round-half-up by frac_bits and the u8-sat or int32 stage, with exact sums for acc_bits >= 64
+ * (128-bit where the sum could pass 2^63).  The row keeps the U-1 stuffed zeros after its last
+ * frame: out_width is exactly width * U.  With channels > 1 the stuffing counts frames, not
+ * interleaved values.  U = 1 is the full-rate result.  There is NO gain: zero-stuffing divides the
+ * passband level by U, and a caller who wants unity passband gain scales the taps by U before
+ * quantizing them.  y is C-contiguous, rows x out_width x channels, uint8 (FIR_OUT_U8_SAT) or
+ * int32 (FIR_OUT_I32).  Computed in polyphase form: output i*U + e sums hq[p + U*t] *
+ * x[i + c - t] over t >= 0 with p + U*t < taps, p = (e + taps/2) mod U, c = (e + taps/2) div U;
+ * x is read once and no stuffed signal is ever stored.  Empty problems (rows or width equal to 0)
+ * are no-ops returning FIR_OK.
+ * Checks, in this order: those of fir1d_fixed_rows_dev with their texts, "up must be >= 1", the
+ * sizes (rows * width * up * channels * 4 must fit in int64), NULL x or y (only when the problem
+ * is not empty), then the device lookup of the host form.
+ * fir_interp_out_width: width * up, or -1 for up < 1, width < 0 or a product past int64.
+ * fir_interp_rows: host pointers, synchronous on `device`.  fir_interp_rows_dev: device pointers,
+ * enqueued on `stream`, never synchronises, does not detect overlap; with 2 <= up <= 16,
+ * taps <= 128 within int16, acc_bits <= 32, frac_bits <= 31, u8 of one channel or int16 of one or
+ * two, x 16-byte aligned (u8: 8) and one row or rows of a multiple of 8 samples (y at any element
+ * address) it allocates nothing and can be captured in a hipGraph (every other call reads its
+ * taps from a cached device table, whose first use cannot be captured).  Added without an ABI
+ * number change (additive, as fir_decim_*). */
+int64_t fir_interp_out_width(int64_t width, int up);
+int fir_interp_rows(const void* x, int in_dtype, int64_t rows, int64_t width, int channels,
+                    const int32_t* hq, int taps, int up, int frac_bits, int acc_bits, int out_stage,
+                    void* y, int device);
+int fir_interp_rows_dev(const void* x_dev, int in_dtype, int64_t rows, int64_t width, int channels,
+                        const int32_t* hq, int taps, int up, int frac_bits, int acc_bits,
+                        int out_stage, void* y_dev, void* stream);
 
 /* F filters of `taps` taps each over the same x: hq is F x taps (row-major), y holds F
  * consecutive output planes shaped like x (plane f at y + f * rows*width*channels elements).

@@ -703,6 +703,31 @@ int fir_decim_rows_dev(const void* x_dev, int in_dtype, int64_t rows, int64_t wi
                      frac_bits, acc_bits, out_stage, y_dev, (hipStream_t)stream);
 }
 
+int64_t fir_interp_out_width(int64_t width, int up) { return fir::interp_out_width(width, up); }
+
+int fir_interp_rows(const void* x, int in_dtype, int64_t rows, int64_t width, int channels, const int32_t* hq, int taps,
+                    int up, int frac_bits, int acc_bits, int out_stage, void* y, int device) {
+    return guarded([&]() -> int {
+        if (const int rc = checked(fir::check_fir1d_interp, in_dtype, rows, width, channels, hq, taps, up, frac_bits,
+                                   acc_bits, out_stage))
+            return rc;
+        if (rows == 0 || width == 0) return FIR_OK;
+        if (!x || !y) return fail(FIR_EINVAL, "x and y must not be NULL");
+        const size_t n = (size_t)(rows * width * channels);
+        return run_host(device, x, n * in_size(in_dtype), y, n * (size_t)up * out_size(out_stage),
+                        [&](void* dx, void* dy, hipStream_t s, std::string* err) {
+                            return fir::launch_fir1d_interp(dx, in_dtype, rows, width, channels, hq, taps, up, frac_bits,
+                                                            acc_bits, out_stage, dy, s, err);
+                        }, 0, 0, 0, true);
+    });
+}
+
+int fir_interp_rows_dev(const void* x_dev, int in_dtype, int64_t rows, int64_t width, int channels, const int32_t* hq,
+                        int taps, int up, int frac_bits, int acc_bits, int out_stage, void* y_dev, void* stream) {
+    return dev_entry(fir::launch_fir1d_interp, x_dev, in_dtype, rows, width, channels, hq, taps, up, frac_bits,
+                     acc_bits, out_stage, y_dev, (hipStream_t)stream);
+}
+
 int fir1d_fixed_rows_multi(const void* x, int in_dtype, int64_t rows, int64_t width, int channels,
                            const int32_t* hq, int taps, int filters, int frac_bits, int acc_bits, int out_stage,
                            void* y, int device) {

@@ -96,6 +96,22 @@ int launch_fir1d_decim(const void* x, int in_dtype, int64_t rows, int64_t width,
                        int decim, int phase, int frac, int acc_bits, int stage, void* y, hipStream_t stream,
                        std::string* err);
 
+// The interpolating row-wise FIR (fir1d_interp.hip): what launch_fir1d_rows gives for x with
+// up - 1 zero frames stuffed after every frame, rows x interp_out_width x ch outputs.
+// interp_out_width: width * up, -1 for up < 1, width < 0 or overflow.  check_fir1d_interp:
+// check_fir1d's checks, then up and the sizes.  interp_path_ok: the LDS polyphase v_dot2 kernel
+// applies (2 <= up <= 16, up to 128 int16 taps, acc_bits <= 32, frac <= 31, u8 of one channel or
+// int16 of one or two, x aligned as decim_path_ok asks, one row or rows of a multiple of 8
+// samples; y at any element address); every other call runs the generic one-output-per-thread
+// kernel.
+int64_t interp_out_width(int64_t width, int up);
+int check_fir1d_interp(int in_dtype, int64_t rows, int64_t width, int ch, const int32_t* hq, int L, int up, int frac,
+                       int acc_bits, int stage, std::string* err);
+bool interp_path_ok(const void* x, int in_dtype, int64_t rows, int64_t width, int ch, const int32_t* hq, int L, int up,
+                    int frac, int acc_bits);
+int launch_fir1d_interp(const void* x, int in_dtype, int64_t rows, int64_t width, int ch, const int32_t* hq, int L,
+                        int up, int frac, int acc_bits, int stage, void* y, hipStream_t stream, std::string* err);
+
 // F filters of L taps (hq row-major F x L) over the same x; y = F consecutive output planes.
 int launch_fir1d_rows_multi(const void* x, int in_dtype, int64_t rows, int64_t width, int ch, const int32_t* hq,
                             int L, int F, int frac, int acc_bits, int stage, void* y, hipStream_t stream,

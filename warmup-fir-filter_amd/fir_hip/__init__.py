@@ -6,11 +6,11 @@ library is missing, no gfx950 device is present, or a HIP call fails.  There is 
 CPU fallback: the product path fails loudly rather than computing elsewhere.
 
 Host-array entry points (NumPy in, NumPy out, synchronous):
-    fir1d_fixed_rows, fir1d_fixed_rows_decim, fir1d_fixed_rows_multi, fir1d_fixed_rows_sharded, fir2d_fixed,
-    fir2d_ideal, fir1d_ideal_rows, compare_metrics, restore_u8, and the stage drivers' image batches
+    fir1d_fixed_rows, fir1d_fixed_rows_decim, fir1d_fixed_rows_interp, fir1d_fixed_rows_multi,
+    fir1d_fixed_rows_sharded, fir2d_fixed, fir2d_ideal, fir1d_ideal_rows, compare_metrics, restore_u8, and the stage drivers' image batches
     fir1d_fixed_images_multi / fir1d_ideal_images_multi (page-locked staging: host_empty)
 Device entry points (torch tensors on a HIP device, enqueued on the current stream):
-    see :mod:`fir_hip.torch_ops`.
+    see :mod:`fir_hip.torch_ops` (and :mod:`fir_hip.torch_interp` for the interpolating FIR).
 """
 from __future__ import annotations
 
@@ -28,6 +28,7 @@ __all__ = [
     "ipc_close", "peek", "IPC_HANDLE_BYTES", "device_bus_id", "peer_access", "peer_atomics", "halo_mailbox_bytes",
     "GATE_TIMEOUT", "GATE_LAYOUT", "build_id", "parse_devices", "METRIC_DTYPES", "fir1d_fixed_images_multi",
     "fir1d_ideal_images_multi", "host_empty", "TIMING_KEYS", "decim_out_width", "fir1d_fixed_rows_decim",
+    "interp_out_width", "fir1d_fixed_rows_interp",
 ]
 
 IN_U8, IN_I16 = 0, 1
@@ -63,6 +64,9 @@ EXPORTS = {
     "fir_decim_out_width": (_i64, [_i64, _i32, _i32]),
     "fir_decim_rows": (_i32, [_vp, _i32, _i64, _i64, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _i32]),
     "fir_decim_rows_dev": (_i32, [_vp, _i32, _i64, _i64, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
+    "fir_interp_out_width": (_i64, [_i64, _i32]),
+    "fir_interp_rows": (_i32, [_vp, _i32, _i64, _i64, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _i32]),
+    "fir_interp_rows_dev": (_i32, [_vp, _i32, _i64, _i64, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
     "fir1d_fixed_rows_multi": (_i32, [_vp, _i32, _i64, _i64, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _i32]),
     "fir1d_fixed_rows_multi_dev": (_i32, [_vp, _i32, _i64, _i64, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
     "fir1d_fixed_images_multi_dev": (_i32, [_i32, _vp, _vp, _vp, _i32, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _vp,
@@ -343,6 +347,49 @@ def fir1d_fixed_rows_decim(x: np.ndarray, hq, decim: int, phase: int = 0, frac_b
     _check(lib().fir_decim_rows(_ptr(x), in_dtype, rows, rowlen // channels, channels, _ptr(h), h.size, int(decim),
                                 int(phase), int(frac_bits), int(acc_bits), int(out_stage), _ptr(y), int(device)),
            "fir_decim_rows")
+    return y
+
+
+def interp_out_width(width: int, up: int) -> int:
+    """Frames a row of ``width`` frames has after zero-stuffing by ``up`` (fir_interp_out_width):
+    width * up; FirHipError for up < 1, a negative width or a product past int64.  Needs no library."""
+    width, up = int(width), int(up)
+    if up < 1:
+        raise FirHipError("up must be >= 1")
+    if width < 0:
+        raise FirHipError("width must be >= 0")
+    if width * up >= 1 << 63:
+        raise FirHipError("width * up does not fit in int64")
+    return width * up
+
+
+def fir1d_fixed_rows_interp(x: np.ndarray, hq, up: int, frac_bits: int = 12, acc_bits: int = 32,
+                            out_stage: int = OUT_U8_SAT, channels: int = 1, device: int = 0,
+                            out: np.ndarray | None = None) -> np.ndarray:
+    """The interpolating FIR: the value of ``fir1d_fixed_rows`` for x with ``up - 1`` zero frames
+    stuffed after every frame (viewed as (..., width, channels): ``xu[..., ::up, :] = x``), computed
+    in polyphase form from x itself, so no stuffed signal is stored and no tap meets a stuffed zero.
+    Returns x's leading axes with a last axis of width * up * channels values.  There is no gain:
+    for unity passband gain scale the taps by ``up`` before quantizing them."""
+    x = np.ascontiguousarray(x)
+    if x.dtype == np.uint8:
+        in_dtype = IN_U8
+    elif x.dtype == np.int16:
+        in_dtype = IN_I16
+    else:
+        raise FirHipError(f"x dtype must be uint8 or int16, got {x.dtype}")
+    h = _taps_i32(hq)
+    if x.ndim == 0:
+        x = x.reshape(1)
+    rowlen = x.shape[-1]
+    rows = x.size // rowlen if rowlen else 0
+    if channels < 1 or rowlen % channels:
+        raise FirHipError("row length must be a multiple of channels")
+    ow = interp_out_width(rowlen // channels, up)
+    y = _out_buf(out, x.shape[:-1] + (ow * channels,), np.uint8 if out_stage == OUT_U8_SAT else np.int32, x)
+    _check(lib().fir_interp_rows(_ptr(x), in_dtype, rows, rowlen // channels, channels, _ptr(h), h.size, int(up),
+                                 int(frac_bits), int(acc_bits), int(out_stage), _ptr(y), int(device)),
+           "fir_interp_rows")
     return y
 
 
