@@ -48,6 +48,9 @@
  *   fir_interp_rows[_dev] none: the reference has no interpolating form; fir1d_fixed_rows of the
  *                         signal with up-1 zero frames after every frame, computed in polyphase
  *                         form from x itself.
+ *   fir_resample_rows[_dev] none: the reference has no resampling form; fir_interp_rows followed by
+ *                         y[..., phase::decim], computed in one pass that neither stores the
+ *                         interpolated signal nor computes a dropped frame.
  *   fir_restore_u8[_dev]  fir_1d/sim/vector/restore_images.py:51-64 (_to_u8_clip,
  *                         _to_u8_normalized), the array half of the restore stage.
  *
@@ -179,6 +182,49 @@ int fir_interp_rows(const void* x, int in_dtype, int64_t rows, int64_t width, in
 int fir_interp_rows_dev(const void* x_dev, int in_dtype, int64_t rows, int64_t width, int channels,
                         const int32_t* hq, int taps, int up, int frac_bits, int acc_bits,
                         int out_stage, void* y_dev, void* stream);
+
+/* ---- rational U/D resampling 1-D fixed-point FIR: zero-stuff by `up`, filter, keep every
+ * decim-th output frame, in one pass ------------------------------------------------------
+ * For up = U >= 1, decim = D >= 1 and 0 <= phase < D:
+ *
+ *   mid_width  = width * U
+ *   out_width  = mid_width > phase ? (mid_width - phase + D - 1) / D : 0
+ *   y[r, m, c] = y_up[r, m*D + phase, c]          m in [0, out_width), c in [0, channels)
+ *
+ * y_up is exactly what fir_interp_rows gives for the same x, hq, up, frac_bits, acc_bits,
+ * out_stage and channels: the same centre rule (taps/2), zero padding at each row's ends, wrap to
+ * acc_bits, round-half-up by frac_bits and the u8-sat or int32 stage, with exact sums for
+ * acc_bits >= 64 (128-bit where the sum could pass 2^63).  There is NO gain (see fir_interp_rows).
+ * `phase` counts frames of y_up; with channels > 1 stuffing and decimation both count frames, not
+ * interleaved values.  y is C-contiguous, rows x out_width x channels, uint8 (FIR_OUT_U8_SAT) or
+ * int32 (FIR_OUT_I32).  U = 1 is fir_decim_rows, D = 1 is fir_interp_rows, U = D = 1 the full-rate
+ * result.  Computed in polyphase form: with a = phase + taps/2 + q*D, output v*U + q (0 <= q < U)
+ * sums hq[p + U*t] * x[v*D + c - t] over t >= 0 with p + U*t < taps, p = a mod U, c = a div U; x
+ * is read once, neither y_up nor any stuffed signal is ever stored, no dropped output is computed.
+ * Empty problems (rows, width or out_width equal to 0, phase >= width * up included) are no-ops
+ * returning FIR_OK.
+ * Checks, in this order: those of fir1d_fixed_rows_dev with their texts, "up must be >= 1",
+ * "decim must be >= 1", "phase must be in [0, decim)", the sizes (width * up, rows * out_width *
+ * channels * 4 and rows * width * channels * 4 must fit in int64), NULL x or y (only when the
+ * problem is not empty), then the device lookup of the host form.
+ * fir_resample_out_width: out_width, or -1 for up < 1, decim < 1, phase outside [0, decim),
+ * width < 0 or a width * up past int64.
+ * fir_resample_rows: host pointers, synchronous on `device`.  fir_resample_rows_dev: device
+ * pointers, enqueued on `stream`, never synchronises, does not detect overlap; with 2 <= up <= 16,
+ * 2 <= decim <= 16, taps within int16 and at most 64 of them per phase (ceil(taps / up) <= 64),
+ * acc_bits <= 32, frac_bits <= 31, u8 of one channel or int16 of one or two, x 16-byte aligned
+ * (u8: 8) and one row or rows of a multiple of 8 samples (y at any element address) it allocates
+ * nothing and can be captured in a hipGraph; with up = 1 or decim = 1 under the conditions of
+ * fir_decim_rows_dev / fir_interp_rows_dev (every other call reads its taps from a cached device
+ * table, whose first use cannot be captured).  Added without an ABI number change (additive, as
+ * fir_interp_*). */
+int64_t fir_resample_out_width(int64_t width, int up, int decim, int phase);
+int fir_resample_rows(const void* x, int in_dtype, int64_t rows, int64_t width, int channels,
+                      const int32_t* hq, int taps, int up, int decim, int phase, int frac_bits,
+                      int acc_bits, int out_stage, void* y, int device);
+int fir_resample_rows_dev(const void* x_dev, int in_dtype, int64_t rows, int64_t width, int channels,
+                          const int32_t* hq, int taps, int up, int decim, int phase, int frac_bits,
+                          int acc_bits, int out_stage, void* y_dev, void* stream);
 
 /* F filters of `taps` taps each over the same x: hq is F x taps (row-major), y holds F
  * consecutive output planes shaped like x (plane f at y + f * rows*width*channels elements).

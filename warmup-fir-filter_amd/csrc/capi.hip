@@ -728,6 +728,36 @@ int fir_interp_rows_dev(const void* x_dev, int in_dtype, int64_t rows, int64_t w
                      acc_bits, out_stage, y_dev, (hipStream_t)stream);
 }
 
+int64_t fir_resample_out_width(int64_t width, int up, int decim, int phase) {
+    return fir::resample_out_width(width, up, decim, phase);
+}
+
+int fir_resample_rows(const void* x, int in_dtype, int64_t rows, int64_t width, int channels, const int32_t* hq,
+                      int taps, int up, int decim, int phase, int frac_bits, int acc_bits, int out_stage, void* y,
+                      int device) {
+    return guarded([&]() -> int {
+        int64_t ow = 0;
+        if (const int rc = checked(fir::check_fir1d_resample, in_dtype, rows, width, channels, hq, taps, up, decim,
+                                   phase, frac_bits, acc_bits, out_stage, &ow))
+            return rc;
+        if (rows == 0 || ow == 0) return FIR_OK;
+        if (!x || !y) return fail(FIR_EINVAL, "x and y must not be NULL");
+        return run_host(device, x, (size_t)(rows * width * channels) * in_size(in_dtype), y,
+                        (size_t)(rows * ow * channels) * out_size(out_stage),
+                        [&](void* dx, void* dy, hipStream_t s, std::string* err) {
+                            return fir::launch_fir1d_resample(dx, in_dtype, rows, width, channels, hq, taps, up, decim,
+                                                              phase, frac_bits, acc_bits, out_stage, dy, s, err);
+                        }, 0, 0, 0, true);
+    });
+}
+
+int fir_resample_rows_dev(const void* x_dev, int in_dtype, int64_t rows, int64_t width, int channels,
+                          const int32_t* hq, int taps, int up, int decim, int phase, int frac_bits, int acc_bits,
+                          int out_stage, void* y_dev, void* stream) {
+    return dev_entry(fir::launch_fir1d_resample, x_dev, in_dtype, rows, width, channels, hq, taps, up, decim, phase,
+                     frac_bits, acc_bits, out_stage, y_dev, (hipStream_t)stream);
+}
+
 int fir1d_fixed_rows_multi(const void* x, int in_dtype, int64_t rows, int64_t width, int channels,
                            const int32_t* hq, int taps, int filters, int frac_bits, int acc_bits, int out_stage,
                            void* y, int device) {

@@ -112,6 +112,25 @@ bool interp_path_ok(const void* x, int in_dtype, int64_t rows, int64_t width, in
 int launch_fir1d_interp(const void* x, int in_dtype, int64_t rows, int64_t width, int ch, const int32_t* hq, int L,
                         int up, int frac, int acc_bits, int stage, void* y, hipStream_t stream, std::string* err);
 
+// The rational resampling row-wise FIR (fir1d_resample.hip): y[r, m, c] = y_up[r, m * decim + phase, c]
+// with y_up what launch_fir1d_interp gives, rows x resample_out_width x ch outputs.
+// resample_out_width: decim_out_width(width * up, decim, phase), -1 for a bad up / decim / phase /
+// width or a width * up past int64.  check_fir1d_resample: check_fir1d's checks, then up, decim,
+// phase and the sizes; *out_width on success.  launch_fir1d_resample forwards up == 1 to
+// launch_fir1d_decim and decim == 1 to launch_fir1d_interp.  resample_path_ok: the LDS polyphase
+// v_dot2 kernel applies (2 <= up, decim <= 16, int16 taps with at most 64 per phase, acc_bits <= 32,
+// frac <= 31, u8 of one channel or int16 of one or two, x aligned as interp_path_ok asks, one row or
+// rows of a multiple of 8 samples; y at any element address); every other call runs the generic
+// one-output-per-thread kernel.
+int64_t resample_out_width(int64_t width, int up, int decim, int phase);
+int check_fir1d_resample(int in_dtype, int64_t rows, int64_t width, int ch, const int32_t* hq, int L, int up, int decim,
+                         int phase, int frac, int acc_bits, int stage, int64_t* out_width, std::string* err);
+bool resample_path_ok(const void* x, int in_dtype, int64_t rows, int64_t width, int ch, const int32_t* hq, int L, int up,
+                      int decim, int frac, int acc_bits, int64_t out_width);
+int launch_fir1d_resample(const void* x, int in_dtype, int64_t rows, int64_t width, int ch, const int32_t* hq, int L,
+                          int up, int decim, int phase, int frac, int acc_bits, int stage, void* y, hipStream_t stream,
+                          std::string* err);
+
 // F filters of L taps (hq row-major F x L) over the same x; y = F consecutive output planes.
 int launch_fir1d_rows_multi(const void* x, int in_dtype, int64_t rows, int64_t width, int ch, const int32_t* hq,
                             int L, int F, int frac, int acc_bits, int stage, void* y, hipStream_t stream,

@@ -6,11 +6,13 @@ library is missing, no gfx950 device is present, or a HIP call fails.  There is 
 CPU fallback: the product path fails loudly rather than computing elsewhere.
 
 Host-array entry points (NumPy in, NumPy out, synchronous):
-    fir1d_fixed_rows, fir1d_fixed_rows_decim, fir1d_fixed_rows_interp, fir1d_fixed_rows_multi,
+    fir1d_fixed_rows, fir1d_fixed_rows_decim, fir1d_fixed_rows_interp, fir1d_fixed_rows_resample,
+    fir1d_fixed_rows_multi,
     fir1d_fixed_rows_sharded, fir2d_fixed, fir2d_ideal, fir1d_ideal_rows, compare_metrics, restore_u8, and the stage drivers' image batches
     fir1d_fixed_images_multi / fir1d_ideal_images_multi (page-locked staging: host_empty)
 Device entry points (torch tensors on a HIP device, enqueued on the current stream):
-    see :mod:`fir_hip.torch_ops` (and :mod:`fir_hip.torch_interp` for the interpolating FIR).
+    see :mod:`fir_hip.torch_ops` (:mod:`fir_hip.torch_interp` for the interpolating FIR, :mod:`fir_hip.torch_resample`
+    for the resampling one).
 """
 from __future__ import annotations
 
@@ -28,7 +30,7 @@ __all__ = [
     "ipc_close", "peek", "IPC_HANDLE_BYTES", "device_bus_id", "peer_access", "peer_atomics", "halo_mailbox_bytes",
     "GATE_TIMEOUT", "GATE_LAYOUT", "build_id", "parse_devices", "METRIC_DTYPES", "fir1d_fixed_images_multi",
     "fir1d_ideal_images_multi", "host_empty", "TIMING_KEYS", "decim_out_width", "fir1d_fixed_rows_decim",
-    "interp_out_width", "fir1d_fixed_rows_interp",
+    "interp_out_width", "fir1d_fixed_rows_interp", "resample_out_width", "fir1d_fixed_rows_resample",
 ]
 
 IN_U8, IN_I16 = 0, 1
@@ -67,6 +69,11 @@ EXPORTS = {
     "fir_interp_out_width": (_i64, [_i64, _i32]),
     "fir_interp_rows": (_i32, [_vp, _i32, _i64, _i64, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _i32]),
     "fir_interp_rows_dev": (_i32, [_vp, _i32, _i64, _i64, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
+    "fir_resample_out_width": (_i64, [_i64, _i32, _i32, _i32]),
+    "fir_resample_rows": (_i32, [_vp, _i32, _i64, _i64, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp,
+                                 _i32]),
+    "fir_resample_rows_dev": (_i32, [_vp, _i32, _i64, _i64, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp,
+                                     _vp]),
     "fir1d_fixed_rows_multi": (_i32, [_vp, _i32, _i64, _i64, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _i32]),
     "fir1d_fixed_rows_multi_dev": (_i32, [_vp, _i32, _i64, _i64, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
     "fir1d_fixed_images_multi_dev": (_i32, [_i32, _vp, _vp, _vp, _i32, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _vp,
@@ -390,6 +397,52 @@ def fir1d_fixed_rows_interp(x: np.ndarray, hq, up: int, frac_bits: int = 12, acc
     _check(lib().fir_interp_rows(_ptr(x), in_dtype, rows, rowlen // channels, channels, _ptr(h), h.size, int(up),
                                  int(frac_bits), int(acc_bits), int(out_stage), _ptr(y), int(device)),
            "fir_interp_rows")
+    return y
+
+
+def resample_out_width(width: int, up: int, decim: int, phase: int = 0) -> int:
+    """Frames a row of ``width`` frames has after zero-stuffing by ``up`` and keeping
+    ``[phase::decim]`` (fir_resample_out_width): decim_out_width(width * up, decim, phase);
+    FirHipError for up < 1, decim < 1, a phase outside [0, decim), a negative width or a width * up
+    past int64.  Needs no library."""
+    width, up, decim, phase = int(width), int(up), int(decim), int(phase)
+    if up < 1:
+        raise FirHipError("up must be >= 1")
+    if decim < 1:
+        raise FirHipError("decim must be >= 1")
+    if not 0 <= phase < decim:
+        raise FirHipError("phase must be in [0, decim)")
+    return decim_out_width(interp_out_width(width, up), decim, phase)
+
+
+def fir1d_fixed_rows_resample(x: np.ndarray, hq, up: int, decim: int, phase: int = 0, frac_bits: int = 12,
+                              acc_bits: int = 32, out_stage: int = OUT_U8_SAT, channels: int = 1, device: int = 0,
+                              out: np.ndarray | None = None) -> np.ndarray:
+    """The rational ``up / decim`` resampling FIR: the value of ``fir1d_fixed_rows_interp(x, hq, up,
+    ...)`` viewed as (..., width * up, channels)``[..., phase::decim, :]``, computed in one polyphase
+    pass that neither stores the interpolated signal nor computes a dropped frame.  Returns x's
+    leading axes with a last axis of resample_out_width(width, up, decim, phase) * channels values.
+    There is no gain: for unity passband gain scale the taps by ``up`` before quantizing them."""
+    x = np.ascontiguousarray(x)
+    if x.dtype == np.uint8:
+        in_dtype = IN_U8
+    elif x.dtype == np.int16:
+        in_dtype = IN_I16
+    else:
+        raise FirHipError(f"x dtype must be uint8 or int16, got {x.dtype}")
+    h = _taps_i32(hq)
+    if x.ndim == 0:
+        x = x.reshape(1)
+    rowlen = x.shape[-1]
+    rows = x.size // rowlen if rowlen else 0
+    if channels < 1 or rowlen % channels:
+        raise FirHipError("row length must be a multiple of channels")
+    ow = resample_out_width(rowlen // channels, up, decim, phase)
+    y = _out_buf(out, x.shape[:-1] + (ow * channels,), np.uint8 if out_stage == OUT_U8_SAT else np.int32, x)
+    _check(lib().fir_resample_rows(_ptr(x), in_dtype, rows, rowlen // channels, channels, _ptr(h), h.size, int(up),
+                                   int(decim), int(phase), int(frac_bits), int(acc_bits), int(out_stage), _ptr(y),
+                                   int(device)),
+           "fir_resample_rows")
     return y
 
 
