@@ -51,6 +51,10 @@
  *   fir_resample_rows[_dev] none: the reference has no resampling form; fir_interp_rows followed by
  *                         y[..., phase::decim], computed in one pass that neither stores the
  *                         interpolated signal nor computes a dropped frame.
+ *   fir_cplx_rows[_dev]   none: the reference has no complex-tap form (lib/mycomplex.h scales a complex
+ *                         value by a real one only); without it the result takes two real filters of
+ *                         twice the taps over the flattened row, each discarding half of its outputs,
+ *                         then an interleave.
  *   fir_restore_u8[_dev]  fir_1d/sim/vector/restore_images.py:51-64 (_to_u8_clip,
  *                         _to_u8_normalized), the array half of the restore stage.
  *
@@ -225,6 +229,37 @@ int fir_resample_rows(const void* x, int in_dtype, int64_t rows, int64_t width, 
 int fir_resample_rows_dev(const void* x_dev, int in_dtype, int64_t rows, int64_t width, int channels,
                           const int32_t* hq, int taps, int up, int decim, int phase, int frac_bits,
                           int acc_bits, int out_stage, void* y_dev, void* stream);
+
+/* ---- complex-coefficient 1-D fixed-point FIR for complex int16 ---------------------------
+ * x: rows x width frames of interleaved int16 (xr, xi), C-contiguous.  hq: taps x 2 int32 (host
+ * memory), (hr[k], hi[k]).  With c = taps / 2 and frames outside a row equal to zero:
+ *
+ *   re[n] = stage(round(wrap_acc( sum_k hr[k] * xr[n-k+c] - hi[k] * xi[n-k+c] )))
+ *   im[n] = stage(round(wrap_acc( sum_k hr[k] * xi[n-k+c] + hi[k] * xr[n-k+c] )))
+ *
+ * wrap_acc, round and stage are those of every fixed entry (above).  Each of the two sums is ONE
+ * exact integer sum of its 2 * taps products, wrapped once to acc_bits; for acc_bits >= 64 the sums
+ * are exact (128-bit where sum_k (|hr[k]| + |hi[k]|) * 32768 could pass 2^63).  y: rows x width x
+ * 2 interleaved (re, im), int32 (FIR_OUT_I32) or sat-u8 per component (FIR_OUT_U8_SAT, accepted
+ * for uniformity; it runs on the generic kernel).  There is no conjugation flag and no gain: a
+ * correlator negates hi itself.  With every hi[k] = 0 the result is fir1d_fixed_rows(...,
+ * channels = 2) with hr, bit for bit (the call is forwarded to it).  Empty problems (rows or width
+ * equal to 0) are no-ops returning FIR_OK.
+ * Checks, in this order: those of fir1d_fixed_rows_dev for FIR_IN_I16 and two channels with their
+ * texts, the sizes (rows * width * 2 * 4 must fit in int64), NULL x or y (only when the problem
+ * is not empty), then the device lookup of the host form.
+ * fir_cplx_rows: host pointers, synchronous on `device`.  fir_cplx_rows_dev: device pointers,
+ * enqueued on `stream`, never synchronises, does not detect overlap; with taps <= 64, both tap
+ * parts within [-32767, 32767] (-hi must fit in int16), acc_bits <= 32, frac_bits <= 31,
+ * FIR_OUT_I32, x AND y 16-byte aligned (the kernel stores whole 16-byte vectors directly) and one
+ * row or rows of a multiple of 4 frames it allocates nothing and can be captured in a hipGraph,
+ * as can a forwarded call under fir1d_fixed_rows_dev's own conditions (every other call reads its
+ * taps from a cached device table, whose first use cannot be captured).  Added without an ABI
+ * number change (additive, as fir_resample_*). */
+int fir_cplx_rows(const int16_t* x, int64_t rows, int64_t width, const int32_t* hq, int taps,
+                  int frac_bits, int acc_bits, int out_stage, void* y, int device);
+int fir_cplx_rows_dev(const int16_t* x_dev, int64_t rows, int64_t width, const int32_t* hq, int taps,
+                      int frac_bits, int acc_bits, int out_stage, void* y_dev, void* stream);
 
 /* F filters of `taps` taps each over the same x: hq is F x taps (row-major), y holds F
  * consecutive output planes shaped like x (plane f at y + f * rows*width*channels elements).

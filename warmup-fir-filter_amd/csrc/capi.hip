@@ -758,6 +758,28 @@ int fir_resample_rows_dev(const void* x_dev, int in_dtype, int64_t rows, int64_t
                      frac_bits, acc_bits, out_stage, y_dev, (hipStream_t)stream);
 }
 
+int fir_cplx_rows(const int16_t* x, int64_t rows, int64_t width, const int32_t* hq, int taps, int frac_bits,
+                  int acc_bits, int out_stage, void* y, int device) {
+    return guarded([&]() -> int {
+        if (const int rc = checked(fir::check_fir1d_cplx, rows, width, hq, taps, frac_bits, acc_bits, out_stage))
+            return rc;
+        if (rows == 0 || width == 0) return FIR_OK;
+        if (!x || !y) return fail(FIR_EINVAL, "x and y must not be NULL");
+        const size_t n = (size_t)(rows * width) * 2;
+        return run_host(device, x, n * sizeof(int16_t), y, n * out_size(out_stage),
+                        [&](void* dx, void* dy, hipStream_t s, std::string* err) {
+                            return fir::launch_fir1d_cplx((const int16_t*)dx, rows, width, hq, taps, frac_bits,
+                                                          acc_bits, out_stage, dy, s, err);
+                        }, 0, 0, 0, true);
+    });
+}
+
+int fir_cplx_rows_dev(const int16_t* x_dev, int64_t rows, int64_t width, const int32_t* hq, int taps, int frac_bits,
+                      int acc_bits, int out_stage, void* y_dev, void* stream) {
+    return dev_entry(fir::launch_fir1d_cplx, x_dev, rows, width, hq, taps, frac_bits, acc_bits, out_stage, y_dev,
+                     (hipStream_t)stream);
+}
+
 int fir1d_fixed_rows_multi(const void* x, int in_dtype, int64_t rows, int64_t width, int channels,
                            const int32_t* hq, int taps, int filters, int frac_bits, int acc_bits, int out_stage,
                            void* y, int device) {

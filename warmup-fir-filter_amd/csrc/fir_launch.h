@@ -131,6 +131,20 @@ int launch_fir1d_resample(const void* x, int in_dtype, int64_t rows, int64_t wid
                           int up, int decim, int phase, int frac, int acc_bits, int stage, void* y, hipStream_t stream,
                           std::string* err);
 
+// The complex-coefficient row-wise FIR for complex int16 (fir1d_cplx.hip): x rows x width frames
+// of interleaved (re, im) int16, hq L x 2 int32 (hr[k], hi[k]), y rows x width x 2 outputs of the
+// stage's type.  check_fir1d_cplx: check_fir1d's checks for int16 of two channels, then the sizes.
+// launch_fir1d_cplx forwards taps whose every hi is 0 to launch_fir1d_rows with channels = 2.
+// cplx_path_ok: the LDS sliding-window v_dot2 kernel applies (up to 64 taps with both parts in
+// [-32767, 32767], acc_bits <= 32, frac <= 31, FIR_OUT_I32, x and y 16-byte aligned, one row or
+// rows of a multiple of 4 frames); every other call runs the generic one-frame-per-thread kernel.
+int check_fir1d_cplx(int64_t rows, int64_t width, const int32_t* hq, int L, int frac, int acc_bits, int stage,
+                     std::string* err);
+bool cplx_path_ok(const void* x, const void* y, int64_t rows, int64_t width, const int32_t* hq, int L, int frac,
+                  int acc_bits, int stage);
+int launch_fir1d_cplx(const int16_t* x, int64_t rows, int64_t width, const int32_t* hq, int L, int frac, int acc_bits,
+                      int stage, void* y, hipStream_t stream, std::string* err);
+
 // F filters of L taps (hq row-major F x L) over the same x; y = F consecutive output planes.
 int launch_fir1d_rows_multi(const void* x, int in_dtype, int64_t rows, int64_t width, int ch, const int32_t* hq,
                             int L, int F, int frac, int acc_bits, int stage, void* y, hipStream_t stream,

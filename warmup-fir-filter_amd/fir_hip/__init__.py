@@ -7,12 +7,12 @@ CPU fallback: the product path fails loudly rather than computing elsewhere.
 
 Host-array entry points (NumPy in, NumPy out, synchronous):
     fir1d_fixed_rows, fir1d_fixed_rows_decim, fir1d_fixed_rows_interp, fir1d_fixed_rows_resample,
-    fir1d_fixed_rows_multi,
+    fir1d_fixed_rows_cplx, fir1d_fixed_rows_multi,
     fir1d_fixed_rows_sharded, fir2d_fixed, fir2d_ideal, fir1d_ideal_rows, compare_metrics, restore_u8, and the stage drivers' image batches
     fir1d_fixed_images_multi / fir1d_ideal_images_multi (page-locked staging: host_empty)
 Device entry points (torch tensors on a HIP device, enqueued on the current stream):
     see :mod:`fir_hip.torch_ops` (:mod:`fir_hip.torch_interp` for the interpolating FIR, :mod:`fir_hip.torch_resample`
-    for the resampling one).
+    for the resampling one, :mod:`fir_hip.torch_cplx` for the complex-tap one).
 """
 from __future__ import annotations
 
@@ -31,6 +31,7 @@ __all__ = [
     "GATE_TIMEOUT", "GATE_LAYOUT", "build_id", "parse_devices", "METRIC_DTYPES", "fir1d_fixed_images_multi",
     "fir1d_ideal_images_multi", "host_empty", "TIMING_KEYS", "decim_out_width", "fir1d_fixed_rows_decim",
     "interp_out_width", "fir1d_fixed_rows_interp", "resample_out_width", "fir1d_fixed_rows_resample",
+    "fir1d_fixed_rows_cplx",
 ]
 
 IN_U8, IN_I16 = 0, 1
@@ -74,6 +75,8 @@ EXPORTS = {
                                  _i32]),
     "fir_resample_rows_dev": (_i32, [_vp, _i32, _i64, _i64, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp,
                                      _vp]),
+    "fir_cplx_rows": (_i32, [_vp, _i64, _i64, _vp, _i32, _i32, _i32, _i32, _vp, _i32]),
+    "fir_cplx_rows_dev": (_i32, [_vp, _i64, _i64, _vp, _i32, _i32, _i32, _i32, _vp, _vp]),
     "fir1d_fixed_rows_multi": (_i32, [_vp, _i32, _i64, _i64, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _i32]),
     "fir1d_fixed_rows_multi_dev": (_i32, [_vp, _i32, _i64, _i64, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
     "fir1d_fixed_images_multi_dev": (_i32, [_i32, _vp, _vp, _vp, _i32, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _vp,
@@ -443,6 +446,48 @@ def fir1d_fixed_rows_resample(x: np.ndarray, hq, up: int, decim: int, phase: int
                                    int(decim), int(phase), int(frac_bits), int(acc_bits), int(out_stage), _ptr(y),
                                    int(device)),
            "fir_resample_rows")
+    return y
+
+
+def _taps_cplx_i32(hq) -> np.ndarray:
+    """A (taps, 2) array of integer (hr[k], hi[k]) pairs as C-contiguous int32; refused before any
+    library call otherwise."""
+    h = np.asarray(hq)
+    if h.ndim != 2 or h.shape[1] != 2 or h.shape[0] == 0:
+        raise FirHipError(f"hq must be a non-empty (taps, 2) array of (hr, hi) pairs, got shape {h.shape}")
+    if h.shape[0] > MAX_TAPS:  # before any copy
+        raise FirHipError(f"{h.shape[0]} taps exceed the library limit of {MAX_TAPS}")
+    # Python ints past int64 arrive as an object array: still integers, refused by their range
+    ints = all(isinstance(v, int) and not isinstance(v, bool) for v in h.flat) if h.dtype == object else \
+        np.issubdtype(h.dtype, np.integer)
+    if not ints:
+        raise FirHipError(f"hq must be an integer array, got {h.dtype}")
+    if int(h.min()) < -(1 << 31) or int(h.max()) >= (1 << 31):
+        raise FirHipError("quantized complex taps must fit in int32")
+    return np.ascontiguousarray(h.astype(np.int64), dtype=np.int32)
+
+
+def fir1d_fixed_rows_cplx(x: np.ndarray, hq, frac_bits: int = 12, acc_bits: int = 32, out_stage: int = OUT_I32,
+                          device: int = 0, out: np.ndarray | None = None) -> np.ndarray:
+    """Row-wise same-mode fixed FIR of complex int16 with COMPLEX taps: x's last axis holds 2 * width
+    interleaved (re, im) values, hq is a (taps, 2) integer array of (hr[k], hi[k]).  Output frame n is
+    the complex sum over k of (hr[k] + j hi[k]) * x[n - k + taps // 2], each part one exact sum wrapped
+    once to acc_bits, rounded by frac_bits; returns x's shape, int32 (OUT_I32) or uint8 per component
+    (OUT_U8_SAT).  No conjugation and no gain: a correlator negates hi itself.  With every hi = 0 it
+    equals fir1d_fixed_rows(x, hr, ..., channels=2) bit for bit."""
+    if not isinstance(x, np.ndarray) or x.dtype != np.int16:
+        raise FirHipError(f"x must be an int16 array of interleaved (re, im), got {getattr(x, 'dtype', type(x).__name__)}")
+    if x.ndim == 0:
+        raise FirHipError("x must have at least one axis of interleaved (re, im) values")
+    if x.shape[-1] % 2:
+        raise FirHipError(f"x's last axis must hold an even number of values (re, im pairs), got {x.shape[-1]}")
+    x = np.ascontiguousarray(x)
+    h = _taps_cplx_i32(hq)
+    rowlen = x.shape[-1]
+    rows = x.size // rowlen if rowlen else 0
+    y = _out_buf(out, x.shape, np.uint8 if out_stage == OUT_U8_SAT else np.int32, x)
+    _check(lib().fir_cplx_rows(_ptr(x), rows, rowlen // 2, _ptr(h), h.shape[0], int(frac_bits), int(acc_bits),
+                               int(out_stage), _ptr(y), int(device)), "fir_cplx_rows")
     return y
 
 
