@@ -28,6 +28,7 @@ import torch_interp_cases as ic
 from fir_hip import torch_interp, torch_ops
 from guarded import guarded_input, guarded_output
 from oracle import c_oracle
+from rate_property_cases import interp_want as _want, stuff as _stuff  # the reference above, stated once
 
 DEV = torch.device("cuda:0")
 PASS = 512  # kIntPass: input frames the workgroup's lanes cover at once, two each
@@ -55,17 +56,6 @@ def _tile(cfg, U):
 def _samples(rng, dtype, rows, width, ch):
     lo, hi = (0, 256) if dtype == np.uint8 else (-32768, 32768)
     return rng.integers(lo, hi, (rows, width * ch), dtype=dtype)
-
-
-def _stuff(x, U, ch):
-    rows, rowlen = x.shape
-    xu = np.zeros((rows, rowlen // ch * U, ch), x.dtype)
-    xu[:, ::U] = x.reshape(rows, rowlen // ch, ch)
-    return xu.reshape(rows, -1)
-
-
-def _want(x, hq, U, frac, acc, stage, ch):
-    return c_oracle().fir1d_rows(_stuff(x, U, ch), hq, frac, acc, stage, channels=ch)
 
 
 def _run(x, hq, U, frac, acc, stage, ch, **kw):

@@ -10,6 +10,9 @@ Complements the fixed parameter grids of test_gpu_fir1d.py / test_gpu_fir2d_idea
 strategies cover every kernel the launchers can pick (register v_dot2 / byte-pair / packed-16 /
 mad24 forms, the generic LDS kernel, the 2-D separable, packed-16 and general forms, the 2-D
 int8 matrix-core kernel forced on, the halo segment path) without enumerating them, and hypothesis shrinks any failure to a small case.
+The four rate-changing / complex families (the decimating, interpolating, resampling and
+complex-tap FIRs, their fast and generic kernels and their forwards) are
+tests/test_gpu_property_rate.py's, which also places x and y at drawn device addresses.
 """
 from __future__ import annotations
 

@@ -33,7 +33,8 @@ import fir_hip
 import torch_resample_cases as rc
 from fir_hip import torch_interp, torch_ops, torch_resample
 from guarded import guarded_input, guarded_output
-from oracle import c_oracle
+# the reference above, stated once for the grid and the property tests
+from rate_property_cases import resample_slice as _slice, resample_up as _up, resample_want as _want
 
 DEV = torch.device("cuda:0")
 PASS = 512  # kResPass: periods the workgroup's lanes cover at once, two each
@@ -75,29 +76,6 @@ def _is_fast(xd, dtype, shape, ch, U, D, hq, acc=32, frac=12):
 def _samples(rng, dtype, rows, width, ch):
     lo, hi = (0, 256) if dtype == np.uint8 else (-32768, 32768)
     return rng.integers(lo, hi, (rows, width * ch), dtype=dtype)
-
-
-def _stuff(x, U, ch):
-    rows, rowlen = x.shape
-    xu = np.zeros((rows, rowlen // ch * U, ch), x.dtype)
-    xu[:, ::U] = x.reshape(rows, rowlen // ch, ch)
-    return xu.reshape(rows, -1)
-
-
-def _up(x, hq, U, frac, acc, stage, ch):
-    """The full-rate result of the stuffed signal as (rows, width * U, ch): what every (D, phase) slices."""
-    rows, rowlen = x.shape
-    if rowlen == 0 or rows == 0:
-        return np.zeros((rows, 0, ch), np.uint8 if stage == fir_hip.OUT_U8_SAT else np.int32)
-    return c_oracle().fir1d_rows(_stuff(x, U, ch), hq, frac, acc, stage, channels=ch).reshape(rows, rowlen // ch * U, ch)
-
-
-def _slice(up, D, phase):
-    return np.ascontiguousarray(up[:, phase::D]).reshape(up.shape[0], -1)
-
-
-def _want(x, hq, U, D, phase, frac, acc, stage, ch):
-    return _slice(_up(x, hq, U, frac, acc, stage, ch), D, phase)
 
 
 def _same(got, want, U, D, phase, ch, what):
