@@ -67,6 +67,7 @@
 #ifndef FIR_HIP_H
 #define FIR_HIP_H
 
+#include <stddef.h>
 #include <stdint.h>
 
 #ifdef __cplusplus
@@ -428,6 +429,31 @@ int fir_compare_metrics(const double* ideal, const void* fixed, int fixed_dtype,
                         int device);
 int fir_compare_metrics_dev(const double* ideal_dev, const void* fixed_dev, int fixed_dtype, int64_t n,
                             double* out_dev, void* work_dev, void* stream);
+
+/* ---- launch record (diagnostics) -----------------------------------------------------
+ * Which kernel instantiation a call launched.  Every launch of the library passes one wrapper
+ * that, while the CALLING THREAD has the log on, notes the kernel, its grid and its block; off
+ * (the default) a launch pays one thread-local flag test and nothing that runs changes.
+ * fir_launch_log_begin: empty this thread's log and turn it on.
+ * fir_launch_log_end: turn it off and write the log to buf as text, NUL-terminated, one launch per
+ *   line in launch order:  name \t gx,gy,gz \t bx,by,bz \t flags \t note \n
+ *   name: the demangled kernel, e.g. "void fir::fir1d_mfma_run_kernel<0, 10, false, 1, 2>(...)";
+ *   flags: where a template argument is a bit mask (the register kernels' FLAGS, the 2-D kernels'
+ *   MODE), its names joined by '|' ("kNtStore|kU8Dot2|kCoal|kEdgeDword|kRagged", "sep|sep16|nowrap"),
+ *   else empty; note: what the form owes to run-time arguments ("mode=fast ksp=10 hs0=0"), else
+ *   empty.  *need = the bytes the text takes (NUL included), always.  FIR_EINVAL when cap < *need
+ *   (or buf is NULL): the log is kept, call again with *need bytes.  FIR_EINVAL too without a
+ *   begin on this thread, and when more than 4096 launches were made since begin: the message
+ *   says how many were dropped and the log is discarded (never a silently truncated log).
+ * fir_kernel_census: the same lines with empty grid / block / note, sorted, for every instantiation
+ *   some launch site of the library can name -- registered while the library loads, whether or not
+ *   it ever runs; needs no device.  buf / cap / need as above.
+ * Launches made by OTHER threads are not recorded: the worker threads of
+ * fir1d_fixed_rows_sharded's row split launch unseen (the Python layer's devices= split likewise);
+ * every other entry launches on its caller's thread.  Added without an ABI number change. */
+void fir_launch_log_begin(void);
+int fir_launch_log_end(char* buf, size_t cap, size_t* need);
+int fir_kernel_census(char* buf, size_t cap, size_t* need);
 
 /* ---- restore-stage u8 conversion -----------------------------------
  * out[i] = u8 of a[i] (float64), n samples:

@@ -57,6 +57,31 @@ int main(void) {
     expect(fir_halo_mailbox_bytes(-1, 0) == -1 && fir_halo_mailbox_bytes(0, -1) == -1, "mailbox bytes negative");
     expect(fir_halo_mailbox_bytes(0, 0) > 0 && fir_halo_mailbox_bytes(16, 16) % 4 == 0, "mailbox bytes");
     expect(strlen(fir_last_error()) > 0, "error text");
+    /* the launch record: no launch is made here, so this covers its buffer contract only */
+    {
+        size_t need = 99;
+        char one[1] = {'x'};
+        expect(fir_launch_log_end(one, sizeof one, &need) == FIR_EINVAL && need == 0, "log end without begin");
+        expect(strstr(fir_last_error(), "begin") != NULL, "log end without begin: message");
+        fir_launch_log_begin();
+        expect(fir_launch_log_end(NULL, 0, &need) == FIR_EINVAL && need == 1, "empty log, no buffer: need 1");
+        expect(fir_launch_log_end(one, sizeof one, &need) == FIR_OK && need == 1 && one[0] == 0, "empty log read");
+        expect(fir_launch_log_end(one, sizeof one, &need) == FIR_EINVAL, "log read twice");
+        fir_launch_log_begin();
+        expect(fir_launch_log_end(one, sizeof one, NULL) == FIR_EINVAL, "log end, NULL need");
+        expect(fir_launch_log_end(one, sizeof one, &need) == FIR_OK, "log kept after a refused read");
+        /* the census: cap = 0, a buffer one byte short, then exactly *need bytes */
+        need = 0;
+        expect(fir_kernel_census(NULL, 0, &need) == FIR_EINVAL && need > 1, "census cap 0");
+        expect(fir_kernel_census(NULL, 0, NULL) == FIR_EINVAL, "census NULL need");
+        const size_t want = need;
+        char* text = malloc(want);
+        expect(fir_kernel_census(text, want - 1, &need) == FIR_EINVAL && need == want, "census one byte short");
+        expect(fir_kernel_census(text, want, &need) == FIR_OK && need == want, "census retry with *need");
+        expect(strlen(text) == want - 1 && text[want - 2] == '\n', "census text fills *need bytes");
+        expect(strstr(text, "fir1d_reg_kernel<") != NULL && strstr(text, "kU8Dot2") != NULL, "census names kernels");
+        free(text);
+    }
     if (!have) {
         uint8_t x[64] = {0}, y[64];
         expect(fir1d_fixed_rows(x, 0, 1, 64, 1, h3, 3, 12, 32, 0, y, 0) == FIR_ENODEV, "no device -> ENODEV");

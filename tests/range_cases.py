@@ -488,6 +488,13 @@ class Case:
     f: int = 0           # banks: the filter that crosses
     path: str | None = None  # FIR2D_PATH
     frames2: bool = False  # also one call with a batch of two frames
+    # What a call's launch log (fir_hip.launch_log) must show.  form: Launch -> bool, "this is the
+    # narrow form the proof admits": every launch of an accept-side call has it, and a reject- or
+    # conservative-side call has at least one launch without it.  runtime: the proof picks a field
+    # of the tap record that the kernel reads at run time, not an instantiation, so the log cannot
+    # tell the sides apart; both sides must then launch `form`, the kernel that reads the field.
+    form: Callable | None = None
+    runtime: bool = False
 
     @property
     def tight(self) -> bool:
@@ -985,6 +992,100 @@ def wide_case():
     h = np.full(1 << 17, -(1 << 31), np.int64)
     return _bump(h, -1, 1), h
 
+
+# ---- the narrow form of each case, as a launch shows it -----------------------------------------
+_REG1D = ("fir1d_reg_kernel", "fir1d_reg_batch_kernel")
+_REG2D = ("fir2d_reg_kernel", "fir2d_pk16_strip_kernel")
+
+
+def _f_u8dot2(l):  # byte-pair v_dot2: no accumulator can wrap, int16 taps
+    return l.kernel in _REG1D and "kU8Dot2" in l.flags
+
+
+def _f_pk16_bank(l):  # the bank kernel with packed-16 filters (which filters: TapsN::pkmode, run time)
+    return l.kernel in _REG1D and "kU8Pk16" in l.flags
+
+
+def _f_mfma_fast(l):  # the matrix-core kernels' FAST form (template argument; the run kernel: its mode)
+    return ((l.kernel == "fir1d_mfma_step_kernel" and l.targs[4] == "true")
+            or (l.kernel == "fir1d_mfma_long_kernel" and l.targs[3] == "true")
+            or (l.kernel == "fir1d_mfma_run_kernel" and l.note.get("mode") == "fast"))
+
+
+def _f_mfma(l):
+    return l.kernel.startswith("fir1d_mfma_")
+
+
+def _f_nowrap2d(l):  # the strip kernel is taken only under nowrap (fir2d.hip:188)
+    return l.kernel == "fir2d_pk16_strip_kernel" or (l.kernel == "fir2d_reg_kernel" and "nowrap" in l.flags)
+
+
+def _f_sep16(l):
+    return l.kernel == "fir2d_reg_kernel" and "sep16" in l.flags
+
+
+def _f_sep(l):
+    return l.kernel == "fir2d_pk16_strip_kernel" or (l.kernel == "fir2d_reg_kernel" and "sep" in l.flags)
+
+
+def _f_pk_unsigned(l):
+    return l.kernel in _REG2D and "pk16" in l.flags and "pksigned" not in l.flags
+
+
+def _f_pk_signed(l):
+    return l.kernel in _REG2D and "pksigned" in l.flags
+
+
+def _f_pk_any(l):
+    return l.kernel in _REG2D and "pk16" in l.flags
+
+
+def _f_pk_hi8(l):
+    return l.kernel in _REG2D and "pkhi8" in l.flags
+
+
+def _f_m2(l):
+    return l.kernel == "fir2d_mfma_kernel"
+
+
+def _f_m2_np1(l):
+    return l.kernel == "fir2d_mfma_kernel" and l.targs[1] == "1"
+
+
+def _f_m2_fast(l):
+    return l.kernel == "fir2d_mfma_kernel" and l.targs[2] == "true"
+
+
+# id prefix -> (form, runtime); the first match holds
+_FORMS = [
+    ("reg-nowrap", _f_u8dot2, False), ("reg-taps16", _f_u8dot2, False),
+    ("noclamp-", _f_u8dot2, True),      # plan_u8_noclamp sets TapsN's clamp bound, read at run time
+    ("pk16-2d-gen3x3-hi8", _f_pk_hi8, False), ("pk16-2d-sep3x3-hi8", _f_pk_hi8, False),
+    ("pk16-2d-gen3x3-u", _f_pk_unsigned, False), ("pk16-2d-gen5x5-u", _f_pk_unsigned, False),
+    ("pk16-2d-sep3x3-u", _f_pk_unsigned, False), ("pk16-2d-sep5x5-u", _f_pk_unsigned, False),
+    ("pk16-2d-gen3x3-s", _f_pk_signed, False), ("pk16-2d-gen5x5-s", _f_pk_signed, False),
+    ("pk16-2d-sep3x3-s-", _f_pk_signed, False), ("pk16-2d-sep5x5-s-", _f_pk_signed, False),
+    ("pk16-2d-sep3x3-split-sc", _f_pk_any, False),
+    ("pk16-", _f_pk16_bank, True),      # plan_u8_pk16 sets each filter's TapsN::pkmode, read at run time
+    ("mfma-fast", _f_mfma_fast, False), ("mfma-tap-32639", _f_mfma, False),
+    ("reg2d-nowrap", _f_nowrap2d, False), ("reg2d-sep16", _f_sep16, False), ("reg2d-sep24", _f_sep, False),
+    ("reg2d-col16", _f_sep16, False),
+    ("mfma2-np", _f_m2_np1, False), ("mfma2-tap-32639", _f_m2, False), ("mfma2-fast", _f_m2_fast, False),
+]
+for _c in CASES:
+    for _prefix, _form, _runtime in _FORMS:
+        if _c.id.startswith(_prefix):
+            _c.form, _c.runtime = _form, _runtime
+            break
+    assert _c.form is not None, _c.id
+
+# the seams: the form and on which sides a launch shows it
+for _sid, _form, _launched in (("reg-frac22-23", _f_u8dot2, [True, False]), ("pk16-s-clamp", _f_pk16_bank, [True, True, True]),
+                               ("mfma-frac22-23", _f_mfma_fast, [True, False]), ("mfma2-frac16-17", _f_m2_fast, [True, False]),
+                               ("mfma2-s-clamp", _f_m2_np1, [True, False, False])):
+    _s = next(s for s in SEAMS if s["id"] == _sid)
+    _s["form"], _s["launched"] = _form, _launched
+assert all("form" in s and len(s["launched"]) == len(s["sides"]) for s in SEAMS)
 
 CASE_IDS = [c.id for c in CASES]
 assert len(set(CASE_IDS)) == len(CASE_IDS)

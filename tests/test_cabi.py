@@ -531,3 +531,103 @@ def test_torch_runtime_shared_only_when_sonames_match(tmp_path):
     (other / "libamdhip64.so").write_bytes(bytes(data))
     assert not fir_hip._runtime_compatible(other, rocm)
     assert not fir_hip._runtime_compatible(tmp_path / "empty", rocm)
+
+
+# ---- the launch record: census and wrapper, without a GPU ---------------------------------------
+CSRC = Path(__file__).resolve().parents[1] / "warmup-fir-filter_amd" / "csrc"
+
+# instantiations per kernel template in the library's census.  A pull request that changes the set
+# of instantiations (a new kernel, another tap bucket, a dispatcher's switch) changes this table and
+# so has to say so.
+CENSUS_COUNTS = {
+    "fir1d_reg_kernel": 792, "fir1d_reg_batch_kernel": 342, "fir2d_reg_kernel": 162, "fir1d_decim_kernel": 96,
+    "fir1d_mfma_run_kernel": 94, "fir1d_lds_kernel": 64, "fir1d_resample_kernel": 48, "fir1d_interp_kernel": 42,
+    "fir2d_pk16_strip_kernel": 27, "fir2d_ideal_reg_kernel": 25, "fir1d_mfma_step_kernel": 24, "fir1d_cplx_kernel": 20,
+    "fir2d_mfma_kernel": 12, "metrics_ragged": 11, "metrics_blocks_any": 10, "fir1d_ideal_reg_kernel": 9,
+    "fir1d_decim_generic_kernel": 8, "fir1d_edges_kernel": 8, "fir1d_generic_kernel": 8, "fir1d_interp_generic_kernel": 8,
+    "fir1d_resample_generic_kernel": 8, "fir1d_mfma_long_kernel": 6, "fir1d_cplx_generic_kernel": 4,
+    "fir2d_generic_kernel": 4, "fir1d_cplx_generic32_kernel": 2, "restore_map_kernel": 2, "fir1d_ideal_kernel": 1,
+    "fir2d_ideal_generic_kernel": 1, "halo_gate_kernel": 1, "halo_mailbox_init_kernel": 1, "metrics_blocks": 1,
+    "metrics_final": 1, "metrics_leaf_kernel": 1, "metrics_prep": 1, "restore_minmax_kernel": 1, "restore_params_kernel": 1,
+}
+
+
+def test_every_launch_goes_through_the_wrapper():
+    """No bare hipLaunchKernelGGL in csrc/: only FIR_LAUNCH's own definition names it."""
+    bare = []
+    for p in sorted(CSRC.iterdir()):
+        if p.suffix in (".hip", ".h"):
+            for n, line in enumerate(p.read_text().splitlines(), 1):
+                if re.search(r"\bhipLaunchKernelGGL\b|<<<", line) and not line.lstrip().startswith("//"):
+                    bare.append(f"{p.name}:{n}")
+    assert bare and all(b.startswith("fir_launch.h:") for b in bare) and len(bare) == 1, bare
+
+
+def test_kernel_census_without_a_device(lib):
+    from collections import Counter
+
+    import census_cases as cc
+
+    census = fir_hip.kernel_census()
+    assert census and len({l.inst for l in census}) == len(census)
+    for l in census:  # every name demangles and parses
+        assert not l.name.startswith("_Z") and "?" not in l.name and l.kernel and l.grid is None, l.name
+    assert sum(CENSUS_COUNTS.values()) == 1846
+    assert dict(Counter(l.kernel for l in census)) == CENSUS_COUNTS
+    fams = Counter(cc.family_of(l) for l in census)
+    assert None not in fams and set(fams) == set(cc.FAMILIES), fams  # one family each, none empty
+    # a bit-mask argument is spelled in words, from the table beside the mask
+    reg = [l for l in census if l.kernel == "fir1d_reg_kernel"]
+    assert all({"kNtStore", "kCoal", "kEdgeDword"} <= l.flags for l in reg)
+    assert any({"kU8Dot2", "kRagged"} <= l.flags for l in reg) and any("kHalo" in l.flags for l in reg)
+    assert {f for l in census if l.kernel == "fir2d_reg_kernel" for f in l.flags} == {
+        "dot2", "sep", "sep16", "nowrap", "pk16", "pksigned", "pkhi8"}
+
+
+def test_launch_log_contract_without_a_device(lib):
+    """begin / end with no launch between, end without begin, and the thread-locality of the log."""
+    import threading
+
+    with fir_hip.launch_log() as log:
+        pass
+    assert log == []
+    need = ctypes.c_size_t(7)
+    assert lib.fir_launch_log_end(None, 0, ctypes.byref(need)) == 1 and need.value == 0
+    assert b"begin" in lib.fir_last_error()
+    seen = []
+
+    def other():  # another thread's end sees no begin: the log is this thread's alone
+        n = ctypes.c_size_t(0)
+        seen.append(lib.fir_launch_log_end(None, 0, ctypes.byref(n)))
+
+    lib.fir_launch_log_begin()
+    t = threading.Thread(target=other)
+    t.start()
+    t.join()
+    assert seen == [1]
+    buf = ctypes.create_string_buffer(1)
+    assert lib.fir_launch_log_end(buf, 1, ctypes.byref(need)) == 0 and need.value == 1
+
+
+def test_launch_log_keeps_the_blocks_own_exception(lib):
+    class Boom(Exception):
+        pass
+
+    with pytest.raises(Boom):
+        with fir_hip.launch_log():
+            lib.fir_launch_log_end(None, 0, ctypes.byref(ctypes.c_size_t(0)))  # the log's end will now fail too ...
+            buf = ctypes.create_string_buffer(1)
+            lib.fir_launch_log_end(buf, 1, ctypes.byref(ctypes.c_size_t(0)))   # ... (read: "end without begin")
+            raise Boom
+    with fir_hip.launch_log() as log:  # and the next block starts clean
+        pass
+    assert log == []
+
+
+def test_launch_name_parsing():
+    split = fir_hip._split_name
+    assert split("void fir::fir1d_mfma_run_kernel<0, 10, false, 1, 2>(unsigned char const*, fir::OutTraits<0>::T*)") == (
+        "fir1d_mfma_run_kernel", ("0", "10", "false", "1", "2"))
+    assert split("void fir::k<fir::A<1, 2>, (fir::E)3>(fir::T<1>)") == ("k", ("fir::A<1, 2>", "(fir::E)3"))
+    assert split("fir::metrics_final(double const*, long)") == ("metrics_final", ())
+    assert split("void fir::metrics_ragged<unsigned short>(double const*)") == ("metrics_ragged", ("unsigned short",))

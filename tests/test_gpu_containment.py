@@ -14,7 +14,11 @@ and so (c), by (a), that every output element was written.  Data is full-range r
 also holds runs of 0 and 255.  ``(x_lead, y_lead)`` are the byte offsets of the views past a
 512-byte boundary, i.e. what the dispatchers' ``x % 16``, ``x % 8`` and ``y % 16`` tests see.
 
-Group -> kernel it is meant to reach <- the dispatch condition that sends it there
+Group -> kernel it reaches <- the dispatch condition that sends it there.  Every row is asserted:
+each call runs under ``fir_hip.launch_log()`` and the log of that same call -- the kernel, its
+template arguments, its flags spelled in words -- is held against the row before the output is
+compared with the oracle, so a case that drifts off its kernel fails here instead of passing on the
+bit-exact fall-back.
 (launch_fir1d_rows, reg_path_ok: fir1d.hip; mfma_path_ok, launch_mfma_t: fir1d_mfma.hip;
 lds_path_ok: fir1d_lds.hip; launch_fir2d: fir2d.hip; launch_fir2d_mfma: fir2d_mfma.hip):
 
@@ -40,11 +44,13 @@ test_mfma_step_kernel      fir1d_mfma_step_kernel<KS = 2 | 3,    10 <= L <= 65 (
                                                                  < 2^(acc-1).  u8 samples reach <true, false> only with
                                                                  frac > 22 (65 taps of 32768 times 255 stay below 2^31)
 test_mfma_step_y_lead      fir1d_generic_kernel                  y % 16 == 4 fails mfma_path_ok and lds_path_ok
-test_mfma_run_kernel       fir1d_mfma_run_kernel (u8, L >= 66)   launch_mfma_t: KS > 3 and u8 samples.  L = 66: one tile,
-                                                                 one chunk; 257: one chunk of 10; 450: one chunk of 16
-                                                                 (2-tile runs, int32 out); 1000, 2048: several chunks
-                                                                 (u8 out: 4-tile runs; int32 out: chunks of <= 16);
-                                                                 x % 16 == 0 and == 8 (mfma_path_ok: x % 8 for u8)
+test_mfma_run_kernel       fir1d_mfma_run_kernel<STAGE, NS,      launch_mfma_t: KS > 3 and u8 samples; launch_mfma_run:
+                           MULTI, TPS> (u8, L >= 66): RUN_FORMS  k-steps of the halo rounded to 16.  L = 66: one chunk of
+                                                                 4; 257: one chunk of 9; 258: one chunk of 10 (the case
+                                                                 this row had meant by 257); 450: one chunk of 16, all
+                                                                 one tile per run; 1000, 2048 (33, 65 k-steps): several
+                                                                 chunks (u8 out: chunks of 6, 4-tile runs; int32 out:
+                                                                 chunks of 12 / 14, 2-tile runs); x % 16 == 0 and == 8
 test_mfma_long_kernel      fir1d_mfma_long_kernel<int16, STAGE,  launch_mfma_t: KS > 3 and int16 samples; launch_mfma_long
                            ACC32, FAST>, chunks of kMlChunk =     picks the form as above.  L = 66 / 481 / 483 / 993 / 995
                            16 k-steps; all six instantiations:    / 4099 -> 4 / 16 / 17 / 32 / 33 / 130 k-steps.
@@ -61,7 +67,9 @@ test_segment_and_edges     fir1d_reg_kernel kHalo (one launch)   launch_fir1d_se
                            | fir1d_generic_kernel with halos     launch_fir1d_edges; total <= halo samples -> generic
 test_rows_multi            fir1d_reg_kernel F = 1..4 (fused u8   launch_fir1d_rows_multi: u8, ch 1, reg_path_ok(x, x)
                            bank, planes at any byte for u8 out;  and (u8 out or plane bytes % 16 == 0), else per filter;
-                           kU8Dot2, or kU8Pk16 for bank "pk16")  launch_reg: F > 1, u8 out and plan_u8_pk16 -> kU8Pk16
+                           kU8Dot2 for bank "q412big", kU8Pk16   launch_reg: F > 1, u8 out and plan_u8_pk16 -> kU8Pk16
+                           for bank "pk16" and for "q412"'s      (one filter of the group that fits is enough: "q412"'s
+                           group with filter 0)                  filter 0 of small taps)
 test_images_multi          fir1d_reg_batch_kernel (kRagged,      launch_fir1d_images_multi: u8 -> u8, ch 1 and
                            kDefer) | per-image dispatch          reg_path_ok(xs[i], xs[i]); an image at x % 16 == 1 and
                                                                  one narrower than 16 + (L-1) take launch_fir1d_rows
@@ -160,14 +168,64 @@ def _same(y: torch.Tensor, want: np.ndarray, tag) -> None:
                              f"index {bad[0]}: {got.reshape(-1)[bad[0]]} != {want.reshape(-1)[bad[0]]}")
 
 
-def _rows(x: np.ndarray, hq, frac=12, acc=32, stage=I32, ch=1, x_lead=0, y_lead=0, tag=()) -> None:
-    """fir1d_fixed_rows_dev on a guarded input into a guarded output: (a) oracle, (b) canaries."""
+# ---- what a call launched (fir_hip.launch_log) ---------------------------------------------
+_CT = {np.uint8: "unsigned char", np.int16: "short", "uint8": "unsigned char", "int16": "short"}
+# the register kernels' flags that name a form (the rest are the fixed store / load policy)
+_FORM_FLAGS = frozenset({"kDot2", "kU8Dot2", "kAcc32", "kRagged", "kMasked", "kHalo", "kU8Pk16", "kU8PkHi8", "kDefer"})
+_BOOL = {True: "true", False: "false"}
+_MFMA_FORM = {"fast": ("true", "true"), "acc32": ("true", "false"), "acclt32": ("false", "false")}  # <ACC32, FAST>
+
+
+def _one(log, kernel: str, tag):
+    """The call made exactly one launch, of `kernel`."""
+    assert [l.kernel for l in log] == [kernel], (tag, [l.inst for l in log])
+    return log[0]
+
+
+def _reg_form(dtype, ch: int, stage: int, hq, frac: int, acc: int, shape, halo: bool = False) -> set:
+    """The form flags launch_reg / launch_reg_flags give ONE filter (fir1d_reg_impl.h), in words."""
+    h = np.asarray(hq, dtype=np.int64)
+    u8 = np.dtype(dtype) == np.uint8
+    taps16 = bool((h >= -32768).all() and (h <= 32767).all())
+    form = set()
+    if u8 and ch == 1 and taps16 and frac <= 22 and 255 * int(np.abs(h).sum()) + (1 << (frac - 1)) < (1 << (acc - 1)):
+        form.add("kU8Dot2")  # byte-pair v_dot2: no sum can wrap
+    elif not u8 and ch == 1 and taps16:
+        form.add("kDot2")
+    if "kU8Dot2" not in form and acc == 32:
+        form.add("kAcc32")
+    vec = 16 if u8 else 8
+    if len(shape) == 2 and shape[0] > 1 and shape[1] % vec:  # rows straddle vectors
+        form.add("kRagged" if stage == U8 and ch == 1 else "kMasked")
+    elif not u8:
+        form.add("kMasked")  # one int16 filter keeps the masked pair compiled in (its code layout)
+    if halo:
+        form.add("kHalo")
+    return form
+
+
+def _is_reg(l, dtype, stage: int, L: int, ch: int, form: set, tag, F: int = 1) -> None:
+    assert l.kernel == "fir1d_reg_kernel", (tag, l.inst)
+    assert (l.targs[0], l.targs[1], l.targs[2], l.targs[3], l.targs[6]) == (_CT[np.dtype(dtype).name], str(stage), str(L),
+                                                                           str(ch), str(F)), (tag, l.inst)
+    assert l.flags & _FORM_FLAGS == form, (tag, sorted(l.flags & _FORM_FLAGS), sorted(form))
+
+
+def _rows(x: np.ndarray, hq, frac=12, acc=32, stage=I32, ch=1, x_lead=0, y_lead=0, tag=(), want=None) -> None:
+    """fir1d_fixed_rows_dev on a guarded input into a guarded output: want(log, tag) on the call's
+    launch log (a kernel name: exactly one launch of it), then (a) oracle, (b) canaries."""
     tag = (x.dtype.name, x.shape, len(hq), frac, acc, stage, ch, x_lead, y_lead) + tuple(tag)
     xg = guarded_input(torch.from_numpy(x), lead_bytes=x_lead, device=DEV)
     y, check = guarded_output(x.shape, _TDT[stage], lead_bytes=y_lead, device=DEV)
     assert xg.data_ptr() % 16 == x_lead % 16 and y.data_ptr() % 16 == y_lead % 16
-    torch_ops.fir1d_fixed_rows_dev(xg, hq, frac, acc, stage, ch, out=y)
+    with fir_hip.launch_log() as log:
+        torch_ops.fir1d_fixed_rows_dev(xg, hq, frac, acc, stage, ch, out=y)
     torch.cuda.synchronize()
+    assert want is not None, "every case names the kernel it reaches"
+    if isinstance(want, str):
+        _one(log, want, tag)
+    else:
+        want(log, tag)
     _same(y, c_oracle().fir1d_rows(x, hq, frac, acc, stage, channels=ch), tag)
     check(str(tag))
     assert torch.equal(xg.cpu(), torch.from_numpy(x)), tag  # the input is only read
@@ -198,10 +256,20 @@ def test_register_kernel(name, dtype, ch, shape):
         else:
             shp = (shape * ch,)
         x = _samples(rng, shp, dtype)
+
+        def reg(hq, frac, acc, stage):
+            form = _reg_form(dtype, ch, stage, hq, frac, acc, shp)
+            return lambda log, tag: _is_reg(_one(log, "fir1d_reg_kernel", tag), dtype, stage, L, ch, form, tag)
+
         for kind, hq in _reg_taps(rng, L).items():
             for stage in STAGES:
-                _rows(x, hq, 12, 32, stage, ch, tag=(kind,))
-        _rows(x, _reg_taps(rng, L)["q412"], 16, 24, I32, ch, tag=("acc24",))
+                form = _reg_form(dtype, ch, stage, hq, 12, 32, shp)
+                # the arithmetic each kind of taps is here for
+                assert ("kU8Dot2" in form) == (name == "u8" and kind != "mad24"), (kind, form)
+                assert ("kDot2" in form) == (name == "i16" and kind != "mad24"), (kind, form)
+                _rows(x, hq, 12, 32, stage, ch, tag=(kind,), want=reg(hq, 12, 32, stage))
+        hq = _reg_taps(rng, L)["q412"]
+        _rows(x, hq, 16, 24, I32, ch, tag=("acc24",), want=reg(hq, 16, 24, I32))
 
 
 @pytest.mark.parametrize("name,dtype,ch", REG_INPUTS, ids=[r[0] for r in REG_INPUTS])
@@ -214,8 +282,8 @@ def test_register_misaligned(name, dtype, ch):
         for L in (3, 9):
             hq = rng.integers(-8192, 8193, L)
             for stage in STAGES:
-                _rows(x, hq, 12, 32, stage, ch, x_lead=item)
-                _rows(x, hq, 12, 32, stage, ch, y_lead=4 if stage == I32 else 1)
+                _rows(x, hq, 12, 32, stage, ch, x_lead=item, want="fir1d_generic_kernel")
+                _rows(x, hq, 12, 32, stage, ch, y_lead=4 if stage == I32 else 1, want="fir1d_generic_kernel")
 
 
 # ---- the LDS v_dot2 kernel --------------------------------------------------------------
@@ -227,15 +295,15 @@ def test_lds_kernel(shape):
     rng = np.random.default_rng(shape[0] * 10000 + shape[1])
     xi, xu = _samples(rng, shape, np.int16), _samples(rng, shape, np.uint8)
     for L in (10, 24, 39):  # int16 -> int32 below kMfmaMinTapsI32
-        _rows(xi, rng.integers(-32768, 32768, L), 12, 32, I32)
-        _rows(xi, rng.integers(-3000, 3001, L), 16, 24, I32)
+        _rows(xi, rng.integers(-32768, 32768, L), 12, 32, I32, want="fir1d_lds_kernel")
+        _rows(xi, rng.integers(-3000, 3001, L), 16, 24, I32, want="fir1d_lds_kernel")
     big = rng.integers(-3000, 3001, 17)
     big[5] = 32640  # one past the matrix-core byte split: MFMA refuses, v_dot2 takes it
     for x in (xi, xu):
         for stage in STAGES:
-            _rows(x, big, 12, 32, stage)
+            _rows(x, big, 12, 32, stage, want="fir1d_lds_kernel")
     for stage in STAGES:  # u8 input 8 bytes off a 16-byte boundary (lds_path_ok: x % 8 == 0)
-        _rows(xu, big, 12, 32, stage, x_lead=8)
+        _rows(xu, big, 12, 32, stage, x_lead=8, want="fir1d_lds_kernel")
 
 
 # ---- the matrix-core step kernel (2 and 3 k-steps) ------------------------------------------
@@ -265,9 +333,14 @@ def test_mfma_step_kernel(name, dtype, stage, L, ks):
         for form, hq, frac, acc in _step_forms(rng, L, dtype):
             assert _form(hq, dtype, frac, acc) == form
             x = _samples(rng, shape, dtype, pin_third=form == "acc32")
-            _rows(x, hq, frac, acc, stage, tag=(form,))
+
+            def step(log, tag, form=form):
+                l = _one(log, "fir1d_mfma_step_kernel", tag)
+                assert l.targs == (_CT[dtype], str(stage), str(ks)) + _MFMA_FORM[form], (tag, l.inst)
+
+            _rows(x, hq, frac, acc, stage, tag=(form,), want=step)
             if dtype == np.uint8 and shape in ((3, 1032), (1, 5128), (40, 8)):
-                _rows(x, hq, frac, acc, stage, x_lead=8, tag=(form,))
+                _rows(x, hq, frac, acc, stage, x_lead=8, tag=(form,), want=step)
 
 
 @pytest.mark.parametrize("name,dtype,stage", STEP_IO, ids=[r[0] for r in STEP_IO])
@@ -276,11 +349,36 @@ def test_mfma_step_y_lead(name, dtype, stage):
     rng = np.random.default_rng(3)
     for L in (10, 40, 65):
         for shape in ((3, 1032), (1, 5128)):
-            _rows(_samples(rng, shape, dtype), _hann(L), 12, 32, stage, y_lead=4)
+            _rows(_samples(rng, shape, dtype), _hann(L), 12, 32, stage, y_lead=4, want="fir1d_generic_kernel")
 
 
 # ---- the matrix-core run kernel (u8, 66 taps and up) ---------------------------------------
-@pytest.mark.parametrize("L", [66, 257, 450, 1000, 2048])
+# L -> stage -> (k-steps per chunk NS, several chunks, tiles per run): launch_mfma_run with the halo
+# rounded to 16 (66 / 257 / 258 / 450 / 1000 / 2048 taps: 4 / 9 / 10 / 16 / 33 / 65 k-steps; past
+# kMrU8One = 32 (u8 out) or kMrC = 16 (int32 out) k-steps the chunk with the least zero padding)
+RUN_FORMS = {
+    66: {U8: (4, False, 1), I32: (4, False, 1)},
+    257: {U8: (9, False, 1), I32: (9, False, 1)},
+    258: {U8: (10, False, 1), I32: (10, False, 1)},
+    450: {U8: (16, False, 1), I32: (16, False, 1)},
+    1000: {U8: (6, True, 4), I32: (12, True, 2)},
+    2048: {U8: (6, True, 4), I32: (14, True, 2)},
+}
+
+
+def _run_form(L: int, stage: int, form: str, hn=None):
+    ns, multi, tps = RUN_FORMS[L][stage]
+
+    def want(log, tag):
+        l = _one(log, "fir1d_mfma_run_kernel", tag)
+        assert l.targs[:4] == (str(stage), str(ns), _BOOL[multi], str(tps)), (tag, l.inst)
+        assert l.note["mode"] == {"fast": "fast", "acc32": "acc32", "acclt32": "acc24"}[form], (tag, l.note)
+        if hn is not None:
+            assert int(l.targs[4]) in hn, (tag, l.inst)
+    return want
+
+
+@pytest.mark.parametrize("L", list(RUN_FORMS))
 def test_mfma_run_kernel(L):
     rng = np.random.default_rng(L)
     for shape in ((3, 3 * 1024 + 24), (16, 1000), (1, 5 * 1024 + 8)):
@@ -289,11 +387,16 @@ def test_mfma_run_kernel(L):
             hq = rng.integers(-amp, amp + 1, L)
             for stage in STAGES:
                 for x_lead in (0, 8):
-                    _rows(x, hq, frac, acc, stage, x_lead=x_lead, tag=(_form(hq, np.uint8, frac, acc),))
+                    form = _form(hq, np.uint8, frac, acc)
+                    # random taps past a byte in every k-step: no high plane is skipped (HN = -1)
+                    _rows(x, hq, frac, acc, stage, x_lead=x_lead, tag=(form,), want=_run_form(L, stage, form, hn=(-1,)))
     x = _samples(rng, (16, 1000), np.uint8)
-    for stage in STAGES:  # the HN = 0 / partial high-plane forms of a one-chunk filter
-        _rows(x, _hann(L), 12, 32, stage, x_lead=8, tag=("hann",))
-        _rows(x, _hann(L, "sinc"), 12, 32, stage, x_lead=8, tag=("sinc",))
+    for stage in STAGES:  # the HN = 0 / partial high-plane forms of a one-chunk filter (u8 out)
+        one = stage == U8 and not RUN_FORMS[L][stage][1]
+        # a Hann window of unity gain over >= 66 taps stays within a byte: no high plane at all
+        _rows(x, _hann(L), 12, 32, stage, x_lead=8, tag=("hann",), want=_run_form(L, stage, "fast", hn=(0,) if one else (-1,)))
+        _rows(x, _hann(L, "sinc"), 12, 32, stage, x_lead=8, tag=("sinc",),
+              want=_run_form(L, stage, "fast", hn=(-1, 2, 4) if one else (-1,)))
 
 
 # ---- the chunked int16 kernel (66 taps and up): six instantiations ---------------------------
@@ -319,7 +422,13 @@ def test_mfma_long_kernel(L, ks, stage, form, want):
     assert _form(hq, np.int16, frac, acc) == want
     for shape in ([(2, 1032)] if L == 4099 else LONG_SHAPES):
         x = _samples(rng, shape, np.int16, pin_third=form == "acc32")
-        _rows(x, hq, frac, acc, stage, tag=(form,))
+
+        def long_kernel(log, tag):
+            l = _one(log, "fir1d_mfma_long_kernel", tag)
+            assert l.targs == ("short", str(stage)) + _MFMA_FORM[want], (tag, l.inst)
+            assert l.note["ks"] == str(ks), (tag, l.note)
+
+        _rows(x, hq, frac, acc, stage, tag=(form,), want=long_kernel)
 
 
 # ---- the generic kernel --------------------------------------------------------------------
@@ -352,13 +461,25 @@ def test_generic_kernel(name):
     if p["amp"] == (1 << 31) - 1:
         hq[0] = (1 << 31) - 1
     for stage in STAGES:
-        _rows(x, hq, p["frac"], p["acc"], stage, p["ch"], x_lead=p["x_lead"], y_lead=p["y_lead"])
+        _rows(x, hq, p["frac"], p["acc"], stage, p["ch"], x_lead=p["x_lead"], y_lead=p["y_lead"],
+              want="fir1d_generic_kernel")
 
 
 # ---- segments with halos -------------------------------------------------------------------
 SEG_INPUTS = [("u8", np.uint8, 1, (3, 9, 31, 64, 257)), ("i16", np.int16, 1, (3, 9, 31, 64, 257)),
               ("i16c2", np.int16, 2, (3, 9))]
 SEG_CASES = [(e, n, d, c, L) for e in ("segment", "edges") for n, d, c, Ls in SEG_INPUTS for L in Ls]
+
+
+def _long_rows_kernel(dtype, stage: int, L: int, n: int) -> str:
+    """launch_fir1d_rows for ONE row of n samples, one channel, int16 taps of 3000 at most, aligned
+    buffers, past the register kernel's 9 taps: the matrix cores from 10 taps (int16 -> int32: from
+    40) when n is a multiple of 8 (step kernel up to three k-steps, then the run kernel for u8 and
+    the chunked one for int16), else the LDS kernel up to 64 taps, else the generic kernel."""
+    mfma_from = 40 if dtype == np.int16 and stage == I32 else 10
+    if L >= mfma_from and n % 8 == 0:
+        return "fir1d_mfma_step_kernel" if _ks(L) <= 3 else "fir1d_mfma_run_kernel" if dtype == np.uint8 else "fir1d_mfma_long_kernel"
+    return "fir1d_lds_kernel" if L <= 64 else "fir1d_generic_kernel"
 
 
 @pytest.mark.parametrize("entry,name,dtype,ch,L", SEG_CASES, ids=[f"{c[0]}-{c[1]}-{c[4]}" for c in SEG_CASES])
@@ -383,12 +504,25 @@ def test_segment_and_edges(entry, name, dtype, ch, L):
                     hlg = None if hl is None else guarded_input(torch.from_numpy(hl), device=DEV)
                     hrg = None if hr is None else guarded_input(torch.from_numpy(hr), device=DEV)
                     y, check = guarded_output(x.shape, _TDT[stage], device=DEV)
-                    if entry == "segment":
-                        torch_ops.fir1d_fixed_segment_dev(xg, hq, hlg, hrg, frac, acc, stage, ch, out=y)
-                    else:
-                        torch_ops.fir1d_fixed_rows_dev(xg, hq, frac, acc, stage, ch, out=y)
-                        torch_ops.fir1d_fixed_edges_dev(xg, hq, y, hlg, hrg, frac, acc, stage, ch)
+                    with fir_hip.launch_log() as log:
+                        if entry == "segment":
+                            torch_ops.fir1d_fixed_segment_dev(xg, hq, hlg, hrg, frac, acc, stage, ch, out=y)
+                        else:
+                            torch_ops.fir1d_fixed_rows_dev(xg, hq, frac, acc, stage, ch, out=y)
+                            torch_ops.fir1d_fixed_edges_dev(xg, hq, y, hlg, hrg, frac, acc, stage, ch)
                     torch.cuda.synchronize()
+                    # the three routes of the table's row
+                    if entry == "segment" and what == "tiles" and L <= 9:  # one launch, the halos in the kernel
+                        form = _reg_form(dtype, ch, stage, hq, frac, acc, x.shape, halo=side != "none")
+                        _is_reg(_one(log, "fir1d_reg_kernel", tag), dtype, stage, L, ch, form, tag)
+                    else:  # the rows dispatch with zero padding, then the edges redone from the halos
+                        assert len(log) == 2, (tag, [l.inst for l in log])
+                        if L <= 9:
+                            _is_reg(log[0], dtype, stage, L, ch, _reg_form(dtype, ch, stage, hq, frac, acc, x.shape), tag)
+                        else:
+                            assert log[0].kernel == _long_rows_kernel(dtype, stage, L, n), (tag, log[0].inst)
+                        edge = "fir1d_generic_kernel" if what == "all_edge" else "fir1d_edges_kernel"
+                        assert log[1].kernel == edge, (tag, log[1].inst)
                     _same(y, co.fir1d_rows(x, hq, frac, acc, stage, channels=ch, halo_left=hl, halo_right=hr), tag)
                     check(str(tag))
 
@@ -397,7 +531,8 @@ def test_segment_and_edges(entry, name, dtype, ch, L):
 def _banks(rng, F: int, L: int) -> dict:
     """Q4.12 taps (the v_dot2 byte-pair form, filter 0 of small taps), and a bank that fits the
     fused u8 kernel's packed-16 form (kU8Pk16: small integers times a power of two; unsigned,
-    signed and high-byte filters, the last one of odd taps when there are several)."""
+    signed and high-byte filters, the last one of odd taps when there are several); "q412big":
+    Q4.12 taps none of whose filters fits it (the plain byte-pair bank)."""
     q412 = rng.integers(-8192, 8193, (F, L))
     q412[0] = rng.integers(-8, 9, L)
     small = rng.integers(-12, 13, (F, L))
@@ -409,7 +544,33 @@ def _banks(rng, F: int, L: int) -> dict:
     for f in range(F):
         if not pk16[f].any():
             pk16[f, 0] = 1 << int(shifts[f, 0])
-    return {"q412": q412, "pk16": pk16}
+    big = rng.integers(4097, 8193, (F, L)) | 1  # odd taps whose sums pass 16 bits: no filter fits the packed-16 form
+    return {"q412": q412, "q412big": big * rng.choice([-1, 1], (F, L)), "pk16": pk16}
+
+
+def _bank_route(log, dtype, shape, F, L, kind, bank, stage, tag) -> None:
+    """launch_fir1d_rows_multi: the fused register kernel over groups of <= 4 filters, or one
+    launch_fir1d_rows per filter."""
+    total = shape[0] * shape[1]
+    fused = dtype == np.uint8 and shape[1] >= 16 + (L - 1) and (stage == U8 or total * 4 % 16 == 0)
+    if not fused:
+        assert len(log) == F and all(l.kernel in ("fir1d_reg_kernel", "fir1d_generic_kernel") and
+                                     (l.kernel != "fir1d_reg_kernel" or l.targs[6] == "1") for l in log), (tag, [l.inst for l in log])
+        if dtype == np.uint8 and shape[1] < 16 + (L - 1):  # rows narrower than a vector and its halo
+            assert all(l.kernel == "fir1d_generic_kernel" for l in log), (tag, [l.inst for l in log])
+        return
+    groups = [min(4, F - f0) for f0 in range(0, F, 4)]
+    assert [l.kernel for l in log] == ["fir1d_reg_kernel"] * len(groups), (tag, [l.inst for l in log])
+    for g, (l, nf) in enumerate(zip(log, groups)):
+        assert (l.targs[0], l.targs[1], l.targs[2], l.targs[6]) == ("unsigned char", str(stage), str(L), str(nf)), (tag, l.inst)
+        assert "kU8Dot2" in l.flags, (tag, l.inst)  # every bank here has int16 taps whose u8 sums cannot wrap
+        assert ("kRagged" in l.flags or "kMasked" in l.flags) == (shape[1] % 16 != 0), (tag, l.inst)
+        if kind == "pk16":
+            assert ("kU8Pk16" in l.flags) == (nf > 1 and stage == U8), (tag, l.inst)
+        elif kind == "q412big":
+            assert "kU8Pk16" not in l.flags, (tag, l.inst)
+        else:  # "q412": filter 0's small taps fit the packed form, and one fitting filter is enough
+            assert ("kU8Pk16" in l.flags) == (g == 0 and nf > 1 and stage == U8), (tag, l.inst)
 
 
 @pytest.mark.parametrize("shape", [(3, 4499), (2, 4096), (5, 17)], ids=str)
@@ -427,14 +588,16 @@ def test_rows_multi(F, shape):
                 for stage in STAGES:
                     tag = (dtype.__name__, F, shape, L, kind, stage)
                     y, check = guarded_output((F,) + shape, _TDT[stage], device=DEV)
-                    torch_ops.fir1d_fixed_rows_multi_dev(xg, bank, 12, 32, stage, out=y)
+                    with fir_hip.launch_log() as log:
+                        torch_ops.fir1d_fixed_rows_multi_dev(xg, bank, 12, 32, stage, out=y)
                     torch.cuda.synchronize()
+                    _bank_route(log, dtype, shape, F, L, kind, bank, stage, tag)
                     for f in range(F):
                         _same(y[f], co.fir1d_rows(x, bank[f], 12, 32, stage), tag + (f,))
                     check(str(tag))
 
 
-@pytest.mark.parametrize("kind", ["q412", "pk16"])
+@pytest.mark.parametrize("kind", ["q412", "q412big", "pk16"])
 @pytest.mark.parametrize("L", [3, 5])
 @pytest.mark.parametrize("F", [4, 6])
 def test_images_multi(F, L, kind):
@@ -453,8 +616,20 @@ def test_images_multi(F, L, kind):
         planes = [guarded_output(s, torch.uint8, lead_bytes=leads[(i + f) % 5], device=DEV) for f in range(F)]
         outs.append([p[0] for p in planes])
         checks.append([p[1] for p in planes])
-    torch_ops.fir1d_fixed_images_multi_dev(xg, bank, 12, 32, U8, outs=outs)
+    with fir_hip.launch_log() as log:
+        torch_ops.fir1d_fixed_images_multi_dev(xg, bank, 12, 32, U8, outs=outs)
     torch.cuda.synchronize()
+    # images 1 (a byte off 16) and 3 (narrower than 16 + L - 1) go per image and filter, on the
+    # generic kernel; images 0 and 2 share the batch kernel, one launch per group of <= 4 filters,
+    # in the deferred-store seam form since image 0's rows (4499) straddle vectors
+    groups = [min(4, F - f0) for f0 in range(0, F, 4)]
+    insts = [l.inst for l in log]
+    assert [l.kernel for l in log] == ["fir1d_generic_kernel"] * (2 * F) + ["fir1d_reg_batch_kernel"] * len(groups), insts
+    for g, (l, nf) in enumerate(zip(log[2 * F:], groups)):
+        assert (l.targs[0], l.targs[1], l.targs[2], l.targs[6]) == ("unsigned char", str(U8), str(L), str(nf)), insts
+        assert {"kU8Dot2", "kRagged", "kDefer"} <= l.flags, insts
+        pk16 = {"pk16": nf > 1, "q412big": False, "q412": g == 0 and nf > 1}[kind]
+        assert ("kU8Pk16" in l.flags) == pk16, (kind, insts)
     for i, x in enumerate(xs):
         for f in range(F):
             _same(outs[i][f], co.fir1d_rows(x, bank[f], 12, 32, U8), (F, L, kind, i, f))
@@ -483,16 +658,45 @@ FIR2D = {
 }
 
 
-def _frames(rng, frames, H, W, hq2, frac, acc, stage, x_lead=0, y_lead=0, tag=()):
+def _fir2d_route(name: str, stage: int, hq2):
+    """What launch_fir2d picks for a case of FIR2D (the table's test_fir2d_* row): the separable
+    register forms (u8 out whose sums fit 16 bits: the packed-16 strip kernel), the general register
+    forms under FIR2D_PATH=reg, the matrix-core kernel with one or two tap planes."""
+    R, C = np.asarray(hq2).shape
+
+    def want(log, tag):
+        if name.startswith("mfma"):
+            l = _one(log, "fir2d_mfma_kernel", tag)
+            assert l.targs[:2] == (str(R), "2" if "two_plane" in name else "1"), (tag, l.inst)
+        elif name.startswith("sep") and stage == U8 and name != "sep3x3_big":
+            l = _one(log, "fir2d_pk16_strip_kernel", tag)
+            assert l.targs[:2] == (str(R), str(C)) and "pk16" in l.flags, (tag, l.inst)
+        else:
+            l = _one(log, "fir2d_reg_kernel", tag)
+            assert l.targs[:3] == (str(R), str(C), str(stage)), (tag, l.inst)
+            assert ("sep" in l.flags) == name.startswith("sep") and ("dot2" in l.flags) == name.startswith("general"), (tag, l.inst)
+            if name == "general3x3_reg" and stage == U8:  # the sharpen kernel's sums fit 16 bits
+                assert "pk16" in l.flags, (tag, l.inst)
+            else:
+                assert "pk16" not in l.flags, (tag, l.inst)
+    return want
+
+
+def _frames(rng, frames, H, W, hq2, frac, acc, stage, x_lead=0, y_lead=0, tag=(), want="fir2d_generic_kernel"):
     co = c_oracle()
     shape = (H, W) if frames == 1 else (frames, H, W)
     x = _samples(rng, shape, np.uint8)
     xg = guarded_input(torch.from_numpy(x), lead_bytes=x_lead, device=DEV)
     y, check = guarded_output(shape, _TDT[stage], lead_bytes=y_lead, device=DEV)
-    torch_ops.fir2d_fixed_dev(xg, hq2, frac, acc, stage, out=y)
+    with fir_hip.launch_log() as log:
+        torch_ops.fir2d_fixed_dev(xg, hq2, frac, acc, stage, out=y)
     torch.cuda.synchronize()
-    want = np.stack([co.fir2d(f, hq2, frac, acc, stage) for f in x.reshape(-1, H, W)]).reshape(shape)
     tag = (frames, H, W, frac, acc, stage, x_lead, y_lead) + tuple(tag)
+    if isinstance(want, str):
+        _one(log, want, tag)
+    else:
+        want(log, tag)
+    want = np.stack([co.fir2d(f, hq2, frac, acc, stage) for f in x.reshape(-1, H, W)]).reshape(shape)
     _same(y, want, tag)
     check(str(tag))
 
@@ -509,8 +713,8 @@ def test_fir2d_paths(name, W, monkeypatch):
     for H in (1, 2, 17, 33):  # 17: one row past a 16-row strip; 33: one past the 32-row strips
         for frames in (1, 3):
             for stage in stages:
-                _frames(rng, frames, H, W, hq2, frac, 32, stage, tag=(name,))
-    _frames(rng, 3, 33, W, hq2, frac, 24, stages[0], tag=(name, "acc24"))
+                _frames(rng, frames, H, W, hq2, frac, 32, stage, tag=(name,), want=_fir2d_route(name, stage, hq2))
+    _frames(rng, 3, 33, W, hq2, frac, 24, stages[0], tag=(name, "acc24"), want=_fir2d_route(name, stages[0], hq2))
 
 
 @pytest.mark.parametrize("why", ["7x7", "W17", "x_lead1", "y_lead1", "y_lead4_i32", "acc40"])
@@ -551,8 +755,14 @@ def test_ideal_rows(L, shape):
     for x_lead, y_lead in ((0, 0), (1, 0), (0, 8), (16, 16)):
         xg = guarded_input(torch.from_numpy(x), lead_bytes=x_lead, device=DEV)
         y, check = guarded_output(shape, torch.float64, lead_bytes=y_lead, device=DEV)
-        torch_ops.fir1d_ideal_rows_dev(xg, h, out=y)
+        with fir_hip.launch_log() as log:
+            torch_ops.fir1d_ideal_rows_dev(xg, h, out=y)
         torch.cuda.synchronize()
+        # up to 9 taps on aligned buffers: the register form (L its template argument); else LDS
+        if L <= 9 and x_lead % 4 == 0 and y_lead % 16 == 0:
+            assert _one(log, "fir1d_ideal_reg_kernel", (L, shape, x_lead, y_lead)).targs[0] == str(L)
+        else:
+            _one(log, "fir1d_ideal_kernel", (L, shape, x_lead, y_lead))
         _same(y, want, (L, shape, x_lead, y_lead))  # compared as uint64 views
         check(str((L, shape, x_lead, y_lead)))
 
@@ -569,8 +779,14 @@ def test_restore_u8(n, policy):
         ag = guarded_input(torch.from_numpy(a), lead_bytes=lead, device=DEV)
         y, check = guarded_output((n,), torch.uint8, lead_bytes=lead, device=DEV)
         work, check_work = guarded_output((wb,), torch.uint8, device=DEV)
-        torch_ops.restore_u8_dev(ag, policy, out=y, work=work)
+        with fir_hip.launch_log() as log:
+            torch_ops.restore_u8_dev(ag, policy, out=y, work=work)
         torch.cuda.synchronize()
+        if policy == fir_hip.RESTORE_CLIP:  # one map, no parameters
+            assert [l.inst for l in log] == ["restore_map_kernel<false>"], (n, lead, [l.inst for l in log])
+        else:  # min / max, the scale, then the map with it
+            assert [l.inst for l in log] == ["restore_minmax_kernel", "restore_params_kernel",
+                                             "restore_map_kernel<true>"], (n, lead, [l.inst for l in log])
         _same(y, want, (n, policy, lead))
         check(f"out {(n, policy, lead)}")
         check_work(f"work {(n, policy, lead)}")
@@ -591,8 +807,21 @@ def test_compare_metrics(n, dtype):
         fg = guarded_input(torch.from_numpy(yf), lead_bytes=f_lead, device=DEV)
         out, check = guarded_output((9,), torch.float64, device=DEV)
         work, check_work = guarded_output((need,), torch.uint8, device=DEV)
-        torch_ops.compare_metrics_dev(ig, fg, out=out, work=work)
+        with fir_hip.launch_log() as log:
+            torch_ops.compare_metrics_dev(ig, fg, out=out, work=work)
         torch.cuda.synchronize()
+        # launch_metrics_t: aligned u8 with a full 8192-sample block: the one streaming pass (vector
+        # loads); other u8: metrics_blocks per part; other types: the scalar metrics_blocks_any<T>;
+        # then the ragged last block and the final sum
+        ks = [l.kernel for l in log]
+        vec, full, ragged = i_lead % 16 == 0 and f_lead % 16 == 0, n // 8192 > 0, n % 8192 > 0
+        if dtype == np.uint8 and vec and full:
+            assert ks == ["metrics_prep", "metrics_leaf_kernel"], (n, i_lead, f_lead, ks)
+        else:
+            blocks = "metrics_blocks" if dtype == np.uint8 else "metrics_blocks_any"
+            assert ks == [blocks] * full + ["metrics_ragged"] * ragged + ["metrics_final"], (n, i_lead, f_lead, ks)
+            ct = {np.uint8: "unsigned char", np.int16: "short", np.float32: "float"}[dtype]
+            assert all(l.targs == (ct,) for l in log if l.kernel in ("metrics_blocks_any", "metrics_ragged")), [l.inst for l in log]
         got = fir_hip.metrics_from_sums(out.cpu().numpy(), n)
         bad = same_metrics(got, want)
         assert not bad, (n, dtype.__name__, i_lead, f_lead, {k: (got[k], want[k]) for k in bad})

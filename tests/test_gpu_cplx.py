@@ -47,6 +47,21 @@ def _is_fast(xd, yd, shape, hq, acc=32, frac=12, stage=I32):
     return taps_ok and aligned and rows_ok and acc <= 32 and frac <= 31 and stage == I32
 
 
+def _route(log, xd, yd, shape, hq, acc, frac, stage, what):
+    """The call's launch log against _is_fast: the LDS kernel, else a generic one; taps that are all
+    real are forwarded to the two-channel row entry, and an empty call launches nothing."""
+    ks = [l.kernel for l in log]
+    h = np.asarray(hq, dtype=object).reshape(-1, 2)
+    if shape[0] * shape[1] == 0:
+        assert ks == [], (what, ks)
+    elif all(int(v) == 0 for v in h[:, 1]):
+        assert len(ks) == 1 and not ks[0].startswith("fir1d_cplx"), (what, ks)
+    elif _is_fast(xd, yd, (shape[0], shape[1] // 2), hq, acc, frac, stage):
+        assert ks == ["fir1d_cplx_kernel"], (what, ks)
+    else:
+        assert len(ks) == 1 and ks[0] in ("fir1d_cplx_generic_kernel", "fir1d_cplx_generic32_kernel"), (what, ks)
+
+
 def _frames(rng, rows, width):
     return rng.integers(-32768, 32768, (rows, 2 * width), dtype=np.int16)
 
@@ -71,8 +86,10 @@ def _check(x, hq, frac=12, acc=32, stage=I32, what="", fast=None, xd=None):
     yd = torch.empty(x.shape, dtype=torch.int32 if stage == I32 else torch.uint8, device=DEV)
     if fast is not None:
         assert _is_fast(xd, yd, (x.shape[0], x.shape[1] // 2), hq, acc, frac, stage) == fast, what
-    out = torch_cplx.fir1d_fixed_rows_cplx_dev(xd, hq, frac, acc, stage, out=yd)
+    with fir_hip.launch_log() as log:
+        out = torch_cplx.fir1d_fixed_rows_cplx_dev(xd, hq, frac, acc, stage, out=yd)
     assert out is yd
+    _route(log, xd, yd, x.shape, hq, acc, frac, stage, what)
     _same(yd.cpu().numpy(), _ref(x, hq, frac, acc, stage), what)
 
 

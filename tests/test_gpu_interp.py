@@ -58,8 +58,26 @@ def _samples(rng, dtype, rows, width, ch):
     return rng.integers(lo, hi, (rows, width * ch), dtype=dtype)
 
 
+def _is_fast(xd, shape, ch, U, hq, acc, frac):
+    """interp_path_ok, from the documented conditions (the module docstring, fir_launch.h)."""
+    u8 = xd.dtype == torch.uint8
+    h = [int(v) for v in np.asarray(hq, dtype=object).reshape(-1)]
+    return (2 <= U <= 16 and len(h) <= 128 and min(h) >= -32768 and max(h) <= 32767 and acc <= 32 and frac <= 31
+            and (ch == 1 or (ch == 2 and not u8)) and xd.data_ptr() % (8 if u8 else 16) == 0
+            and (shape[0] == 1 or shape[1] % 8 == 0))
+
+
 def _run(x, hq, U, frac, acc, stage, ch, **kw):
-    y = torch_interp.fir1d_fixed_rows_interp_dev(torch.from_numpy(x).to(DEV), hq, U, frac, acc, stage, ch, **kw)
+    """The device entry, its launch log held against _is_fast (an empty output launches nothing)."""
+    xd = torch.from_numpy(x).to(DEV)
+    with fir_hip.launch_log() as log:
+        y = torch_interp.fir1d_fixed_rows_interp_dev(xd, hq, U, frac, acc, stage, ch, **kw)
+    ks = [l.kernel for l in log]
+    if y.numel() == 0:
+        assert ks == [], ks
+    else:
+        fast = _is_fast(xd, x.shape, ch, U, hq, acc, frac)
+        assert ks == ["fir1d_interp_kernel" if fast else "fir1d_interp_generic_kernel"], (U, len(hq), x.shape, ks)
     return y.cpu().numpy()
 
 

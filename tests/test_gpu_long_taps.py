@@ -60,7 +60,15 @@ def test_int16_2p24_long_filter_vs_c_oracle(L):
     x = rng.integers(-32768, 32768, 1 << 24, dtype=np.int16)
     hq = rng.integers(-3000, 3000, L)
     co = c_oracle()
-    got = fir_hip.fir1d_fixed_rows(x, hq, 12, 32, fir_hip.OUT_I32)
+    with fir_hip.launch_log() as log:
+        got = fir_hip.fir1d_fixed_rows(x, hq, 12, 32, fir_hip.OUT_I32)
+    # 65 taps are three k-steps, the step kernel's last length; past it the chunked int16 kernel,
+    # in its acc32 form (random taps of 3000 over full-range samples can wrap 32 bits)
+    insts = [l.inst for l in log]
+    if L == 65:
+        assert insts == ["fir1d_mfma_step_kernel<short, 1, 3, true, false>"], insts
+    else:
+        assert insts == ["fir1d_mfma_long_kernel<short, 1, true, false>"], insts
     assert np.array_equal(got, co.fir1d_rows(x, hq, 12, 32, co.OUT_I32))
 
 
@@ -74,8 +82,14 @@ def test_long_filter_rows_vs_oracle(L, shape, stage, dtype):
     x = rng.integers(lo, hi, shape, dtype=dtype)
     hq = rng.integers(-400, 400, L)
     co = c_oracle()
+    # the matrix cores take rows of a multiple of 8 samples up to 32 accumulator bits (int16: the
+    # chunked kernel, u8: the run kernel); the other shapes and acc 48 are the generic kernel's
+    fast = "fir1d_mfma_long_kernel" if dtype == np.int16 else "fir1d_mfma_run_kernel"
     for frac, acc in ((12, 32), (16, 24), (20, 48)):
-        got = fir_hip.fir1d_fixed_rows(x, hq, frac, acc, stage)
+        with fir_hip.launch_log() as log:
+            got = fir_hip.fir1d_fixed_rows(x, hq, frac, acc, stage)
+        want = fast if shape[1] % 8 == 0 and acc <= 32 else "fir1d_generic_kernel"
+        assert [l.kernel for l in log] == [want], (frac, acc, [l.inst for l in log])
         assert np.array_equal(got, co.fir1d_rows(x, hq, frac, acc, stage)), (frac, acc)
 
 
@@ -189,10 +203,14 @@ def test_acc64_wide_sums_are_exact():
     want = _exact_out(full, hq, [hl_n + i for i in eidx], 12, 80, fo.OUT_U8_SAT)
     got = y.cpu().numpy()
     assert [int(got[i]) for i in eidx] == want
-    # 2-D: 2^23 taps of near-2^31 on u8 pixels reach 2^62 * 255 > 2^63
+    # 2-D: 255 * sum|h| >= 2^63 takes 16 843 010 taps of 2^31 - 1 (the 2^23 taps this case had held
+    # reach 2^62 only, and ran the 64-bit kernel): 4096 x 4113 of them, and the launch log says so
     img = np.full((3, 5), 255, np.uint8)
-    k2 = np.full((1 << 11, 1 << 12), (1 << 31) - 1, np.int64)
-    got2 = fir_hip.fir2d_fixed(img, k2, 12, 100, fir_hip.OUT_I32)
+    k2 = np.full((1 << 12, 4113), (1 << 31) - 1, np.int64)
+    assert 255 * int(k2.sum()) >= 1 << 63
+    with fir_hip.launch_log() as log:
+        got2 = fir_hip.fir2d_fixed(img, k2, 12, 100, fir_hip.OUT_I32)
+    assert [l.inst for l in log] == ["fir2d_generic_kernel<1, true>"], [l.inst for l in log]
     # every output sees the 3 x 5 frame (all 255) under taps of one value: sum = 15 * 255 * h
     s = 15 * 255 * ((1 << 31) - 1)
     q = ((s + (1 << 11)) >> 12) & 0xFFFFFFFF
@@ -249,12 +267,38 @@ def test_table_cache_evicts_only_idle_tables():
             fir_hip.fir1d_fixed_rows(xs, hq, 12, 32, fir_hip.OUT_U8_SAT)
 
 
-# every instantiation of fir1d_mfma_run_kernel: one chunk of 4 .. 12 k-steps (one tile per run,
+# every chunking of fir1d_mfma_run_kernel: one chunk of 4 .. 12 k-steps (one tile per run,
 # 290 / 322 taps: 11 / 12), 14, 16 (354-450 taps), u8 out 18 .. 32 (500-930 taps; int32 out: several
-# chunks of 8 .. 16 past 16); several chunks of 6 and 8 (4-tile runs, u8 out past 32)
-@pytest.mark.parametrize("L", [65, 66, 100, 129, 130, 162, 194, 257, 258, 290, 322, 354, 386, 449, 450, 500, 580, 660,
-                               720, 800, 860, 900, 930, 1000, 2048,
-                               2658, 4099])
+# chunks of 8 .. 16 past 16); several chunks of 6 and 8 (4-tile runs, u8 out past 32).
+# L -> (u8 out, int32 out), each (k-steps per chunk NS, several chunks, tiles per run): the kernel's
+# <STAGE, NS, MULTI, TPS>, worked out from launch_mfma_run / mfma_run_ns (fir1d_mfma.hip) and asserted
+# on every call's launch log.  65 taps are three k-steps: the step kernel's last length, kept as the
+# boundary below the run kernel.
+_ONE = lambda ns: ((ns, False, 1), (ns, False, 1))  # noqa: E731  one chunk, both stages
+RUN_KERNEL = {
+    65: "step", 66: _ONE(4), 100: _ONE(5), 129: _ONE(5), 130: _ONE(6), 162: _ONE(7), 194: _ONE(8), 257: _ONE(9),
+    258: _ONE(10), 290: _ONE(11), 322: _ONE(12), 354: _ONE(14), 386: _ONE(14), 449: _ONE(16), 450: _ONE(16),
+    500: ((18, False, 1), (10, True, 2)), 580: ((20, False, 1), (10, True, 2)), 660: ((22, False, 1), (12, True, 2)),
+    720: ((24, False, 1), (12, True, 2)), 800: ((26, False, 1), (14, True, 2)), 860: ((28, False, 1), (14, True, 2)),
+    900: ((30, False, 1), (10, True, 2)), 930: ((32, False, 1), (16, True, 2)), 1000: ((6, True, 4), (12, True, 2)),
+    2048: ((6, True, 4), (14, True, 2)), 2658: ((8, True, 4), (8, True, 2)), 4099: ((6, True, 4), (10, True, 2)),
+}
+
+
+def _run_launch(log, L: int, stage: int, tag):
+    """The one launch of a u8 long-filter call, held against RUN_KERNEL[L]."""
+    assert len(log) == 1, (tag, [l.inst for l in log])
+    l = log[0]
+    if RUN_KERNEL[L] == "step":
+        assert l.kernel == "fir1d_mfma_step_kernel" and l.targs[:3] == ("unsigned char", str(stage), "3"), (tag, l.inst)
+        return l
+    ns, multi, tps = RUN_KERNEL[L][stage]
+    assert l.kernel == "fir1d_mfma_run_kernel", (tag, l.inst)
+    assert l.targs[:4] == (str(stage), str(ns), "true" if multi else "false", str(tps)), (tag, l.inst)
+    return l
+
+
+@pytest.mark.parametrize("L", list(RUN_KERNEL))
 def test_u8_long_filter_run_kernel_vs_oracle(L):
     """u8 filters past 64 taps (fir1d_mfma_run_kernel: runs of 1-2 tiles sharing each chunk of
     tap fragments, LDS-DMA windows): every chunk length and one- or several-chunk form, rows
@@ -268,7 +312,9 @@ def test_u8_long_filter_run_kernel_vs_oracle(L):
         for frac, acc, amp in ((12, 32, 400), (16, 24, 3000), (12, 32, 32639)):
             hq = rng.integers(-amp, amp + 1, L)
             for stage in (fir_hip.OUT_U8_SAT, fir_hip.OUT_I32):
-                got = fir_hip.fir1d_fixed_rows(x, hq, frac, acc, stage)
+                with fir_hip.launch_log() as log:
+                    got = fir_hip.fir1d_fixed_rows(x, hq, frac, acc, stage)
+                _run_launch(log, L, stage, (shape, frac, acc, amp, stage))
                 want = co.fir1d_rows(x, hq, frac, acc, stage)
                 assert np.array_equal(got, want), (shape, frac, acc, amp, stage)
 
@@ -302,7 +348,39 @@ def _mixed_plane_filters(L: int, rng) -> dict:
     return f
 
 
-@pytest.mark.parametrize("L", [66, 100, 129, 162, 257, 290, 386, 450, 580, 800, 930])
+def _high_plane_form(hq, L: int) -> int:
+    """HN of a one-chunk u8-out filter, as launch_mfma_run (fir1d_mfma.hip) takes it: the k-steps
+    whose taps leave a signed byte, a run of at most 2 or 4 of them kept (when at least twice as
+    many are dropped), none (0), or both planes everywhere (-1)."""
+    c = L // 2
+    P = (L - 1 - c + 15) & ~15
+    ks = (32 + c + P + 31) // 32
+    ksp = ks if ks <= 12 else (ks + 1) & ~1  # one chunk (ks <= 32)
+    steps = [st for t in range(L) if not -128 <= int(hq[t]) <= 127
+             for st in range((c + P - t) // 32, (c + P - t + 31) // 32 + 1) if st < ksp]
+    need = max(steps) - min(steps) + 1 if steps else 0
+    hn = 0 if need == 0 else 2 if need <= 2 else 4 if need <= 4 else -1
+    return -1 if hn > 0 and ksp < 3 * hn else hn
+
+
+HIGH_PLANE_L = [66, 100, 129, 162, 257, 290, 386, 450, 580, 800, 930]
+
+
+def test_high_plane_filters_cover_every_form():
+    """Over its parameters the test below takes HN = -1, 0, 2 and 4 (each call asserts the HN it
+    launched against _high_plane_form), and the filters named for a form take it."""
+    seen = set()
+    for L in HIGH_PLANE_L:
+        f = _mixed_plane_filters(L, np.random.default_rng(1000 + L))
+        seen |= {_high_plane_form(h, L) for h in f.values()}
+        assert _high_plane_form(f["smooth"], L) == 0 and _high_plane_form(f["edge_127"], L) == 0  # all taps in a byte
+        if L >= 386:  # >= 14 k-steps: one large tap keeps a run of 2, the sinc's centre lobe one of <= 4
+            assert _high_plane_form(f["spike_mid"], L) == 2 and _high_plane_form(f["sinc"], L) in (2, 4)
+            assert _high_plane_form(f["spikes_far"], L) == -1  # large taps at both ends: every k-step between
+    assert seen == {-1, 0, 2, 4}
+
+
+@pytest.mark.parametrize("L", HIGH_PLANE_L)
 def test_u8_long_filter_high_plane_skip_vs_oracle(L):
     rng = np.random.default_rng(1000 + L)
     co = c_oracle()
@@ -311,7 +389,10 @@ def test_u8_long_filter_high_plane_skip_vs_oracle(L):
         x[0, :] = 255
         for name, hq in _mixed_plane_filters(L, rng).items():
             for frac, acc in ((12, 32), (14, 24)):
-                got = fir_hip.fir1d_fixed_rows(x, hq, frac, acc, fir_hip.OUT_U8_SAT)
+                with fir_hip.launch_log() as log:
+                    got = fir_hip.fir1d_fixed_rows(x, hq, frac, acc, fir_hip.OUT_U8_SAT)
+                l = _run_launch(log, L, fir_hip.OUT_U8_SAT, (shape, name, frac, acc))
+                assert int(l.targs[4]) == _high_plane_form(hq, L), (shape, name, frac, acc, l.inst, l.note)
                 want = co.fir1d_rows(x, hq, frac, acc, fir_hip.OUT_U8_SAT)
                 assert np.array_equal(got, want), (shape, name, frac, acc)
 

@@ -7,9 +7,11 @@ pointers here; misaligned device pointers, and guard bands around every device b
 tests/test_gpu_containment.py's.
 
 Complements the fixed parameter grids of test_gpu_fir1d.py / test_gpu_fir2d_ideal.py: the
-strategies cover every kernel the launchers can pick (register v_dot2 / byte-pair / packed-16 /
+strategies are aimed at the kernels the launchers can pick (register v_dot2 / byte-pair / packed-16 /
 mad24 forms, the generic LDS kernel, the 2-D separable, packed-16 and general forms, the 2-D
-int8 matrix-core kernel forced on, the halo segment path) without enumerating them, and hypothesis shrinks any failure to a small case.
+int8 matrix-core kernel forced on, the halo segment path) without enumerating them, and hypothesis
+shrinks any failure to a small case.  Which instantiations a test actually launches is not claimed
+here: tests/test_gpu_kernel_census.py holds the launched set against the library's census.
 The four rate-changing / complex families (the decimating, interpolating, resampling and
 complex-tap FIRs, their fast and generic kernels and their forwards) are
 tests/test_gpu_property_rate.py's, which also places x and y at drawn device addresses.

@@ -8,8 +8,11 @@ Unlike test_gpu_property.py the calls go to the DEVICE entries, with x inside gu
 ``out=`` a guarded_output view at drawn leads, so the dispatchers' alignment branches see real
 misaligned device pointers and every store outside the output is caught.  Each strategy draws the
 route it intends (fast kernel, a generic kernel for one named reason, a forward) and builds a call
-that takes it; the test holds ``route_of`` on the real pointers against that route, so a strategy
-that stopped reaching a kernel fails instead of passing quietly.  A forwarded call must also equal
+that takes it; the test holds ``route_of`` on the real pointers against that route, and the route
+OBSERVED in the call's own launch log (``fir_hip.launch_log``: the family's fast kernel, its generic
+kernel, or the kernels of the entry it forwards to) against both, so a strategy that stopped
+reaching a kernel, or a restated dispatcher that drifted from the library's, fails instead of
+passing quietly.  A forwarded call must also equal
 the entry it is forwarded to, run on the same guarded x.  A fifth test sends the same cases through
 the NumPy host entries with a misaligned host array and ``out=``.
 
@@ -74,6 +77,34 @@ def _forwarded(c: rc.Case, xd):
     return torch_ops.fir1d_fixed_rows_dev(xd, [hr for hr, _ in c.hq], c.frac, c.acc, c.stage, channels=2)
 
 
+# The kernels of each route, by family; a forward runs the kernels of the entry it is handed to.
+FAST_KERNEL = {"decim": "fir1d_decim_kernel", "interp": "fir1d_interp_kernel", "resample": "fir1d_resample_kernel",
+               "cplx": "fir1d_cplx_kernel"}
+GENERIC_KERNELS = {"decim": {"fir1d_decim_generic_kernel"}, "interp": {"fir1d_interp_generic_kernel"},
+                   "resample": {"fir1d_resample_generic_kernel"},
+                   "cplx": {"fir1d_cplx_generic_kernel", "fir1d_cplx_generic32_kernel"}}
+FORWARD_KERNELS = {"decim": {FAST_KERNEL["decim"]} | GENERIC_KERNELS["decim"],
+                   "interp": {FAST_KERNEL["interp"]} | GENERIC_KERNELS["interp"],
+                   "rows2": {"fir1d_reg_kernel", "fir1d_generic_kernel", "fir1d_lds_kernel", "fir1d_mfma_step_kernel",
+                             "fir1d_mfma_long_kernel"}}
+
+
+def observed_route(c: rc.Case, log) -> str:
+    """The route a call took, read from its launch log: "fast", "generic", "forward", or "none" for a
+    call that launched nothing (an empty output)."""
+    ks = [l.kernel for l in log]
+    if not ks:
+        return "none"
+    assert len(ks) == 1, (c, [l.inst for l in log])
+    if ks[0] == FAST_KERNEL[c.family]:
+        return "fast"
+    if ks[0] in GENERIC_KERNELS[c.family]:
+        return "generic"
+    to = rc.forwarded_to(c)
+    assert to is not None and ks[0] in FORWARD_KERNELS[to], (c, [l.inst for l in log])
+    return "forward"
+
+
 # Example counts.  The yardstick is test_gpu_property.test_fir1d_rows_random_vs_oracle (1000 examples)
 # in the same pytest run: no test here may take longer.  Measured on an MI355X at 400 examples each:
 # decim 1.54 s, resample 1.32 s, interp 1.12 s, cplx 0.95 s, the yardstick 2.20 s (nearly all of it is
@@ -90,8 +121,11 @@ def _check(c: rc.Case):
     assert xd.data_ptr() % 512 == c.x_lead and (ref.size == 0 or yd.data_ptr() % 512 == c.y_lead), c
     assert rc.route_of(c, xd.data_ptr(), yd.data_ptr()) == c.route, c
     SEEN[c.family][c.route] += 1
-    assert _call(c, xd, yd) is yd
+    with fir_hip.launch_log() as log:
+        assert _call(c, xd, yd) is yd
     torch.cuda.synchronize()
+    seen = observed_route(c, log)
+    assert seen == ("none" if ref.size == 0 else c.route.split(":")[0]), (c, seen, [l.inst for l in log])
     bad = rc.describe_mismatch(c, yd.cpu().numpy(), ref)
     assert bad is None, bad
     guards(f"{c.family} [{c.route}] {c}")

@@ -64,19 +64,50 @@ def _same(got, want, tag, x, names, taps, frame: bool):
                          f"sum(h < 0) = {rc.nsum(taps)}")
 
 
+def _form(c, name, log, tag, route=None, beside=()):
+    """The call's launch log against the case's form (range_cases.Case.form): on the accept side
+    every launch has the narrow form; on the reject and conservative sides at least one launch has
+    not (a bank split per filter keeps it for the filters that do not cross); a run-time proof
+    (Case.runtime) launches it on both sides.  route: the shape is in the list because it takes
+    another kernel, named here: every launch is that kernel, on both sides.  beside: kernels that
+    part of the call is known to take whatever the side, left out of the form's account."""
+    insts = [l.inst for l in log]
+    assert log, (tag, "nothing launched")
+    log = [l for l in log if l.kernel not in beside]
+    assert log, (tag, "every launch took", beside, insts)
+    if route is not None:
+        assert all(l.kernel in route for l in log), (tag, "route", route, insts)
+    elif name == "accept" or c.runtime:
+        assert all(c.form(l) for l in log), (tag, "the narrow form was not launched", insts)
+    else:
+        assert not all(c.form(l) for l in log), (tag, "the narrow form was launched past its proof", insts)
+
+
 def _run_rows(c, name, side, shapes, single=()):
     """One filter through fir1d_fixed_rows; ``single``: widths of rows that also go alone (one row per call)."""
     co = c_oracle()
     for stage in c.stages:
         for w in shapes:
             x, names = _inputs(c.id, name, w)
-            got = fir_hip.fir1d_fixed_rows(x, side.taps, side.frac, side.acc, stage)
+            with fir_hip.launch_log() as log:
+                got = fir_hip.fir1d_fixed_rows(x, side.taps, side.frac, side.acc, stage)
+            # int16 -> int32 below 40 taps never reaches the matrix cores (fir1d.hip, kMfmaMinTapsI32):
+            # at that stage these cases run the LDS kernel on both sides and show the proof at the u8
+            # stage alone
+            lds = c.row == "launch_mfma_t" and c.dtype == np.int16 and stage == rc.I32 and side.taps.size < 40
+            _form(c, name, log, f"{c.id} [{name} side] stage {STAGE_NAME[stage]} rows x {w}",
+                  route=("fir1d_lds_kernel",) if lds else None)
             want = co.fir1d_rows(x, side.taps, side.frac, side.acc, stage)
             _same(got, want, f"{c.id} [{name} side] stage {STAGE_NAME[stage]} rows x {w}", x, names, side.taps, False)
         for w in single:
             x, names = _inputs(c.id, name, w)
             for r in (0, 1):  # the phase-0 high and low rows
-                got = fir_hip.fir1d_fixed_rows(x[r], side.taps, side.frac, side.acc, stage)
+                with fir_hip.launch_log() as log:
+                    got = fir_hip.fir1d_fixed_rows(x[r], side.taps, side.frac, side.acc, stage)
+                # one row of no whole number of 8 samples: the matrix cores refuse it on both sides
+                # (mfma_path_ok), the LDS kernel takes up to 64 taps, the generic kernel the rest
+                _form(c, name, log, f"{c.id} [{name} side] one row of {w}",
+                      route=("fir1d_lds_kernel",) if side.taps.size <= 64 else ("fir1d_generic_kernel",))
                 want = co.fir1d_rows(x[r], side.taps, side.frac, side.acc, stage)
                 _same(got[None], want[None], f"{c.id} [{name} side] stage {STAGE_NAME[stage]} one row of {w}", x[r:r + 1],
                       names[r:r + 1], side.taps, False)
@@ -87,7 +118,23 @@ def _run_bank(c, name, side, shapes):
     for stage in c.stages:
         for w in shapes:
             x, names = _inputs(c.id, name, w)
-            got = fir_hip.fir1d_fixed_rows_multi(x, side.taps, side.frac, side.acc, stage)
+            with fir_hip.launch_log() as log:
+                got = fir_hip.fir1d_fixed_rows_multi(x, side.taps, side.frac, side.acc, stage)
+            # int32 planes of no whole number of 16 bytes (rows x 1283): the bank goes out filter by
+            # filter (launch_fir1d_rows_multi), and a filter whose plane starts off 16 bytes takes the
+            # generic kernel on both sides; the form is held on the filters the register kernel keeps
+            tag = f"{c.id} [{name} side] stage {STAGE_NAME[stage]} bank rows x {w}"
+            if stage == rc.I32 and x.size * 4 % 16 != 0:
+                # one launch per filter, in order; the proof shows in the launch of the filter that
+                # crosses (c.f), unless its plane starts off 16 bytes: then that filter runs the
+                # generic kernel on both sides and this shape shows the proof at the u8 stage alone
+                assert len(log) == len(side.taps), (tag, [l.inst for l in log])
+                if c.f * x.size * 4 % 16 != 0:
+                    _form(c, name, log[c.f:c.f + 1], tag, route=("fir1d_generic_kernel",))
+                else:
+                    _form(c, name, log[c.f:c.f + 1], tag)
+            else:
+                _form(c, name, log, tag)
             for f, h in enumerate(side.taps):
                 want = co.fir1d_rows(x, h, side.frac, side.acc, stage)
                 _same(got[f], want, f"{c.id} [{name} side] stage {STAGE_NAME[stage]} filter {f} rows x {w}", x, names, h, False)
@@ -102,7 +149,10 @@ def _run_frames(c, name, side, monkeypatch, path, stages, frames2, cid):
     for stage in stages:
         for shape in ((64, 1040), (29, 64)):
             x, names = _inputs(cid, name, shape) if cid in CASES else rc.worst_frames_u8(side.taps, *shape)
-            got = np.stack([fir_hip.fir2d_fixed(f, side.taps, side.frac, side.acc, stage) for f in x])
+            with fir_hip.launch_log() as log:
+                got = np.stack([fir_hip.fir2d_fixed(f, side.taps, side.frac, side.acc, stage) for f in x])
+            if c is not None:
+                _form(c, name, log, f"{cid} [{name} side] FIR2D_PATH={path} stage {STAGE_NAME[stage]} frames of {shape}")
             want = np.stack([co.fir2d(f, side.taps, side.frac, side.acc, stage) for f in x])
             tag = f"{cid} [{name} side] FIR2D_PATH={path} stage {STAGE_NAME[stage]} frames of {shape}"
             _same(got, want, tag, x, names, side.taps, True)
@@ -159,8 +209,11 @@ def test_images_multi_plan_threshold_bank(cid):
         x1, n1 = _inputs(c.id, name, 1283)
         imgs = [(np.array(x4), n4), (np.array(x1), n1), (np.array(x1[:1, :1031]), n1[:1])]
         plan = torch_ops.ImagesMultiPlan([torch.from_numpy(a).to(DEV) for a, _ in imgs], side.taps, side.frac, side.acc, rc.U8)
-        outs = plan.launch()
+        with fir_hip.launch_log() as log:
+            outs = plan.launch()
         torch.cuda.synchronize()
+        assert [l.kernel for l in log] == ["fir1d_reg_batch_kernel"], [l.inst for l in log]
+        _form(c, name, log, f"{c.id} [{name} side] one batch")
         for i, (a, names) in enumerate(imgs):
             for f, h in enumerate(side.taps):
                 _same(outs[i][f].cpu().numpy(), co.fir1d_rows(a, h, side.frac, side.acc, rc.U8),
@@ -211,19 +264,24 @@ def test_dispatch_seams(sid, monkeypatch):
     same values in either form (range_cases.SEAMS says why), and both must equal the oracle."""
     s = SEAMS[sid]
     co = c_oracle()
+    import types
+    form = types.SimpleNamespace(form=s["form"], runtime=False)
     for i, side in enumerate(s["sides"]):
         name = f"side {i}, frac {side.frac}"
+        held = "accept" if s["launched"][i] else "reject"  # whether this side's launches show the form
         if s["kind"] == "frame":
-            _run_frames(None, name, side, monkeypatch, s["path"], s["stages"], False, sid)
+            _run_frames(form, held, side, monkeypatch, s["path"], s["stages"], False, sid)
             continue
         for w in (4096, 1283) if s["row"] != "launch_mfma_t" else (2048, 1000):
             h0 = side.taps[0] if s["kind"] == "bank" else side.taps
             x, names = rc.worst_rows_u8(h0, w)
             for stage in s["stages"]:
-                if s["kind"] == "bank":
-                    got = fir_hip.fir1d_fixed_rows_multi(x, side.taps, side.frac, side.acc, stage)
-                else:
-                    got = fir_hip.fir1d_fixed_rows(x, side.taps, side.frac, side.acc, stage)[None]
+                with fir_hip.launch_log() as log:
+                    if s["kind"] == "bank":
+                        got = fir_hip.fir1d_fixed_rows_multi(x, side.taps, side.frac, side.acc, stage)
+                    else:
+                        got = fir_hip.fir1d_fixed_rows(x, side.taps, side.frac, side.acc, stage)[None]
+                _form(form, held, log, f"{sid} [{name}] stage {STAGE_NAME[stage]} rows x {w}")
                 for f, h in enumerate(np.atleast_2d(side.taps)):
                     _same(got[f], co.fir1d_rows(x, h, side.frac, side.acc, stage),
                           f"{sid} [{name}] stage {STAGE_NAME[stage]} filter {f} rows x {w}", x, names, h, False)

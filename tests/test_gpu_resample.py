@@ -90,7 +90,21 @@ def _same(got, want, U, D, phase, ch, what):
 
 
 def _run(xd, hq, U, D, phase, frac, acc, stage, ch, **kw):
-    return torch_resample.fir1d_fixed_rows_resample_dev(xd, hq, U, D, phase, frac, acc, stage, ch, **kw).cpu().numpy()
+    """The device entry, its launch log held against _is_fast (U == 1 and D == 1 are forwarded to the
+    decimator and the interpolator; an empty output launches nothing)."""
+    with fir_hip.launch_log() as log:
+        y = torch_resample.fir1d_fixed_rows_resample_dev(xd, hq, U, D, phase, frac, acc, stage, ch, **kw)
+    ks = [l.kernel for l in log]
+    dtype = np.uint8 if xd.dtype == torch.uint8 else np.int16
+    if y.numel() == 0:
+        assert ks == [], ks
+    elif U == 1 or D == 1:
+        assert len(ks) == 1 and ks[0].startswith("fir1d_decim" if U == 1 else "fir1d_interp"), (U, D, ks)
+    elif _is_fast(xd, dtype, (xd.shape[0], xd.shape[1] // ch), ch, U, D, [int(v) for v in np.asarray(hq).reshape(-1)], acc, frac):
+        assert ks == ["fir1d_resample_kernel"], (U, D, len(hq), ks)
+    else:
+        assert ks == ["fir1d_resample_generic_kernel"], (U, D, len(hq), ks)
+    return y.cpu().numpy()
 
 
 def _check(x, hq, U, D, phases, frac, acc, stage, ch, what, xd=None):

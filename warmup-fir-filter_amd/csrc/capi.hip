@@ -1167,4 +1167,14 @@ int fir_peek(const void* dev_ptr, void* host_out, int64_t bytes) {
     });
 }
 
+void fir_launch_log_begin(void) { fir::launch_log_begin(); }
+
+int fir_launch_log_end(char* buf, size_t cap, size_t* need) {
+    return guarded([&] { return checked(fir::launch_log_end, buf, cap, need); });
+}
+
+int fir_kernel_census(char* buf, size_t cap, size_t* need) {
+    return guarded([&] { return checked(fir::kernel_census, buf, cap, need); });
+}
+
 }  // extern "C"

@@ -177,11 +177,11 @@ static hipError_t launch_generic(const void* x, void* y, int64_t start, int64_t 
     const int64_t blocks = (end - start + kGenTile - 1) / kGenTile;
     if (blocks >= ((int64_t)1 << 31)) return hipErrorInvalidValue;
     if (needs_wide(sizeof(InT) == 1 ? FIR_IN_U8 : FIR_IN_I16, hq, L, acc_bits))
-        hipLaunchKernelGGL((fir1d_generic_kernel<InT, STAGE, true>), dim3((unsigned)blocks), dim3(kBlock), 0, stream,
+        FIR_LAUNCH((fir1d_generic_kernel<InT, STAGE, true>), dim3((unsigned)blocks), dim3(kBlock), 0, stream,
                            (const InT*)x, (OutT*)y, start, end, total, rowlen, multi_row ? 1 : 0, (int64_t)ch,
                            (const InT*)hl, (const InT*)hr, td, L, gen_tap_chunk(L, ch), frac, acc_bits);
     else
-        hipLaunchKernelGGL((fir1d_generic_kernel<InT, STAGE, false>), dim3((unsigned)blocks), dim3(kBlock), 0, stream,
+        FIR_LAUNCH((fir1d_generic_kernel<InT, STAGE, false>), dim3((unsigned)blocks), dim3(kBlock), 0, stream,
                            (const InT*)x, (OutT*)y, start, end, total, rowlen, multi_row ? 1 : 0, (int64_t)ch,
                            (const InT*)hl, (const InT*)hr, td, L, gen_tap_chunk(L, ch), frac, acc_bits);
     return hipGetLastError();
@@ -203,11 +203,11 @@ static hipError_t launch_edges(const void* x, void* y, int64_t total, int ch, co
                                hipStream_t stream) {
     const int64_t blocks = std::min<int64_t>((hle + hre + kBlock - 1) / kBlock, 1024);
     if (wide)
-        hipLaunchKernelGGL((fir1d_edges_kernel<InT, STAGE, true>), dim3((unsigned)blocks), dim3(kBlock), 0, stream,
+        FIR_LAUNCH((fir1d_edges_kernel<InT, STAGE, true>), dim3((unsigned)blocks), dim3(kBlock), 0, stream,
                            (const InT*)x, (typename OutTraits<STAGE>::T*)y, total, (int64_t)ch, (const InT*)hl,
                            (const InT*)hr, td, L, hle, hre, frac, acc_bits);
     else
-        hipLaunchKernelGGL((fir1d_edges_kernel<InT, STAGE, false>), dim3((unsigned)blocks), dim3(kBlock), 0, stream,
+        FIR_LAUNCH((fir1d_edges_kernel<InT, STAGE, false>), dim3((unsigned)blocks), dim3(kBlock), 0, stream,
                            (const InT*)x, (typename OutTraits<STAGE>::T*)y, total, (int64_t)ch, (const InT*)hl,
                            (const InT*)hr, td, L, hle, hre, frac, acc_bits);
     return hipGetLastError();

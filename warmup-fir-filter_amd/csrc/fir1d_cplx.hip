@@ -304,10 +304,10 @@ static hipError_t launch_cplx_lp(const void* x, void* y, int64_t total, int64_t 
     }
     const unsigned blocks = (unsigned)((total + kCxTile - 1) / kCxTile);
     if (acc_bits == 32)
-        hipLaunchKernelGGL((fir1d_cplx_kernel<LP, true>), dim3(blocks), dim3(kBlock), 0, s, (const uint32_t*)x,
+        FIR_LAUNCH((fir1d_cplx_kernel<LP, true>), dim3(blocks), dim3(kBlock), 0, s, (const uint32_t*)x,
                            (int32_t*)y, total, rowlen, t, 0, frac);
     else
-        hipLaunchKernelGGL((fir1d_cplx_kernel<LP, false>), dim3(blocks), dim3(kBlock), 0, s, (const uint32_t*)x,
+        FIR_LAUNCH((fir1d_cplx_kernel<LP, false>), dim3(blocks), dim3(kBlock), 0, s, (const uint32_t*)x,
                            (int32_t*)y, total, rowlen, t, 32 - acc_bits, frac);
     return hipGetLastError();
 }
@@ -348,7 +348,7 @@ static hipError_t launch_cplx_generic(const void* x, void* y, int64_t rows, int6
         const uint32_t* pd = (const uint32_t*)device_table(pk.data(), sizeof(uint32_t) * pk.size(), &err);
         if (!pd) return hipErrorOutOfMemory;
         TableHold hold(pd, s);
-        hipLaunchKernelGGL((fir1d_cplx_generic32_kernel<STAGE>), dim3((unsigned)blocks), dim3(kBlock), 0, s,
+        FIR_LAUNCH((fir1d_cplx_generic32_kernel<STAGE>), dim3((unsigned)blocks), dim3(kBlock), 0, s,
                            (const uint32_t*)x, (OutT*)y, total, width, pd, L, 32 - acc_bits, frac);
         return hipGetLastError();
     }
@@ -356,10 +356,10 @@ static hipError_t launch_cplx_generic(const void* x, void* y, int64_t rows, int6
     if (!td) return hipErrorOutOfMemory;
     TableHold hold(td, s);
     if (needs_wide(FIR_IN_I16, hq, 2 * L, acc_bits))
-        hipLaunchKernelGGL((fir1d_cplx_generic_kernel<STAGE, true>), dim3((unsigned)blocks), dim3(kBlock), 0, s,
+        FIR_LAUNCH((fir1d_cplx_generic_kernel<STAGE, true>), dim3((unsigned)blocks), dim3(kBlock), 0, s,
                            (const int16_t*)x, (OutT*)y, total, width, td, L, frac, acc_bits);
     else
-        hipLaunchKernelGGL((fir1d_cplx_generic_kernel<STAGE, false>), dim3((unsigned)blocks), dim3(kBlock), 0, s,
+        FIR_LAUNCH((fir1d_cplx_generic_kernel<STAGE, false>), dim3((unsigned)blocks), dim3(kBlock), 0, s,
                            (const int16_t*)x, (OutT*)y, total, width, td, L, frac, acc_bits);
     return hipGetLastError();
 }

@@ -314,7 +314,7 @@ static hipError_t launch_decim_lp(const void* x, void* y, int64_t rows, int64_t 
     const int64_t groups = (out_width + (int64_t)G * kDecT - 1) / ((int64_t)G * kDecT);
     const size_t lds = (size_t)CH * D * PL * sizeof(uint32_t);
     using OutT = typename OutTraits<STAGE>::T;
-    hipLaunchKernelGGL((fir1d_decim_kernel<InT, STAGE, CH, LP, ODD>), dim3((unsigned)(rows * groups)), dim3(kBlock),
+    FIR_LAUNCH((fir1d_decim_kernel<InT, STAGE, CH, LP, ODD>), dim3((unsigned)(rows * groups)), dim3(kBlock),
                        lds, s, (const InT*)x, (OutT*)y, width, out_width, (uint32_t)groups, G, D, base, PL, magic,
                        taps, 32 - acc_bits, frac);
     return hipGetLastError();
@@ -357,11 +357,11 @@ static hipError_t launch_decim_generic(const void* x, void* y, int64_t rows, int
     if (!td) return hipErrorOutOfMemory;
     TableHold hold(td, s);
     if (needs_wide(sizeof(InT) == 1 ? FIR_IN_U8 : FIR_IN_I16, hq, L, acc_bits))
-        hipLaunchKernelGGL((fir1d_decim_generic_kernel<InT, STAGE, true>), dim3((unsigned)blocks), dim3(kBlock), 0, s,
+        FIR_LAUNCH((fir1d_decim_generic_kernel<InT, STAGE, true>), dim3((unsigned)blocks), dim3(kBlock), 0, s,
                            (const InT*)x, (OutT*)y, n_out, width, out_width, (int64_t)ch, (int64_t)D, (int64_t)phase,
                            td, L, frac, acc_bits);
     else
-        hipLaunchKernelGGL((fir1d_decim_generic_kernel<InT, STAGE, false>), dim3((unsigned)blocks), dim3(kBlock), 0, s,
+        FIR_LAUNCH((fir1d_decim_generic_kernel<InT, STAGE, false>), dim3((unsigned)blocks), dim3(kBlock), 0, s,
                            (const InT*)x, (OutT*)y, n_out, width, out_width, (int64_t)ch, (int64_t)D, (int64_t)phase,
                            td, L, frac, acc_bits);
     return hipGetLastError();

@@ -369,7 +369,7 @@ static hipError_t launch_interp_np(const void* x, void* y, int64_t rows, int64_t
     const uint32_t stage_bytes = (uint32_t)(T * U * CH) * (uint32_t)sizeof(OutT) + 16u;
     const size_t lds = (size_t)CH * PL * sizeof(uint32_t) + int_phys(stage_bytes) + 4;
     const int64_t groups = (width + F - 1) / F;
-    hipLaunchKernelGGL((fir1d_interp_kernel<InT, STAGE, CH, NP>), dim3((unsigned)(rows * groups)), dim3(kBlock), lds, s,
+    FIR_LAUNCH((fir1d_interp_kernel<InT, STAGE, CH, NP>), dim3((unsigned)(rows * groups)), dim3(kBlock), lds, s,
                        (const InT*)x, (OutT*)y, width, (uint32_t)groups, U, T, S, PL, taps, 32 - acc_bits, frac);
     return hipGetLastError();
 }
@@ -403,10 +403,10 @@ static hipError_t launch_interp_generic(const void* x, void* y, int64_t rows, in
     if (!td) return hipErrorOutOfMemory;
     TableHold hold(td, s);
     if (needs_wide(sizeof(InT) == 1 ? FIR_IN_U8 : FIR_IN_I16, hq, L, acc_bits))
-        hipLaunchKernelGGL((fir1d_interp_generic_kernel<InT, STAGE, true>), dim3((unsigned)blocks), dim3(kBlock), 0, s,
+        FIR_LAUNCH((fir1d_interp_generic_kernel<InT, STAGE, true>), dim3((unsigned)blocks), dim3(kBlock), 0, s,
                            (const InT*)x, (OutT*)y, n_out, width, (int64_t)ch, (int64_t)U, td, L, frac, acc_bits);
     else
-        hipLaunchKernelGGL((fir1d_interp_generic_kernel<InT, STAGE, false>), dim3((unsigned)blocks), dim3(kBlock), 0, s,
+        FIR_LAUNCH((fir1d_interp_generic_kernel<InT, STAGE, false>), dim3((unsigned)blocks), dim3(kBlock), 0, s,
                            (const InT*)x, (OutT*)y, n_out, width, (int64_t)ch, (int64_t)U, td, L, frac, acc_bits);
     return hipGetLastError();
 }

@@ -193,10 +193,10 @@ static hipError_t launch_lds_lp(const void* x, void* y, int64_t total, int64_t r
     const unsigned blocks = (unsigned)((total + kLdsTile - 1) / kLdsTile);
     using OutT = typename OutTraits<STAGE>::T;
     if (acc_bits == 32)
-        hipLaunchKernelGGL((fir1d_lds_kernel<InT, STAGE, LP, true>), dim3(blocks), dim3(kBlock), 0, s, (const InT*)x,
+        FIR_LAUNCH((fir1d_lds_kernel<InT, STAGE, LP, true>), dim3(blocks), dim3(kBlock), 0, s, (const InT*)x,
                            (OutT*)y, total, rowlen, t, 0, frac);
     else
-        hipLaunchKernelGGL((fir1d_lds_kernel<InT, STAGE, LP, false>), dim3(blocks), dim3(kBlock), 0, s, (const InT*)x,
+        FIR_LAUNCH((fir1d_lds_kernel<InT, STAGE, LP, false>), dim3(blocks), dim3(kBlock), 0, s, (const InT*)x,
                            (OutT*)y, total, rowlen, t, 32 - acc_bits, frac);
     return hipGetLastError();
 }

@@ -521,13 +521,13 @@ static hipError_t launch_mfma_long(const void* x, void* y, int64_t rl, int64_t t
     const int64_t want = (ntiles + kMfWaves - 1) / kMfWaves;
     const unsigned blocks = (unsigned)(want < kMlBlocks ? want : kMlBlocks);
     if (fast)
-        hipLaunchKernelGGL((fir1d_mfma_long_kernel<InT, STAGE, true, true>), dim3(blocks), dim3(kBlock), 0, s,
+        FIR_LAUNCH_NOTE("ks=" + std::to_string(KS), (fir1d_mfma_long_kernel<InT, STAGE, true, true>), dim3(blocks), dim3(kBlock), 0, s,
                            (const InT*)x, (OutT*)y, rl, tpr, ntiles, fr, KS, P, bias, 0, frac);
     else if (acc_bits == 32)
-        hipLaunchKernelGGL((fir1d_mfma_long_kernel<InT, STAGE, true, false>), dim3(blocks), dim3(kBlock), 0, s,
+        FIR_LAUNCH_NOTE("ks=" + std::to_string(KS), (fir1d_mfma_long_kernel<InT, STAGE, true, false>), dim3(blocks), dim3(kBlock), 0, s,
                            (const InT*)x, (OutT*)y, rl, tpr, ntiles, fr, KS, P, bias, 0, frac);
     else
-        hipLaunchKernelGGL((fir1d_mfma_long_kernel<InT, STAGE, false, false>), dim3(blocks), dim3(kBlock), 0, s,
+        FIR_LAUNCH_NOTE("ks=" + std::to_string(KS), (fir1d_mfma_long_kernel<InT, STAGE, false, false>), dim3(blocks), dim3(kBlock), 0, s,
                            (const InT*)x, (OutT*)y, rl, tpr, ntiles, fr, KS, P, bias, 32 - acc_bits, frac);
     return hipGetLastError();
 }
@@ -955,13 +955,18 @@ static hipError_t launch_mfma_run(const void* x, void* y, int64_t rl, int64_t tp
         if (hn > 0 && ksp < 3 * hn) hn = -1;
         if (hn > 0) hs0 = smin < ksp - hn ? smin : ksp - hn;
     }
+    // the forms the run kernel takes from run-time arguments, for the launch record
+    const auto note = [&] {
+        return std::string("mode=") + (mode == 0 ? "fast" : "acc" + std::to_string(acc_bits)) + " ksp=" + std::to_string(ksp) +
+               " hs0=" + std::to_string(hs0);
+    };
     auto go = [&](auto nsc, auto mc) {
         constexpr int NS = decltype(nsc)::value;
         constexpr bool M = decltype(mc)::value;
         if constexpr (!M && NS <= kMrT1Ns) {
             auto one = [&](auto hnc) {
                 constexpr int H = decltype(hnc)::value;
-                hipLaunchKernelGGL((fir1d_mfma_run_kernel<STAGE, NS, M, 1, H>), dim3(blocks), dim3(kBlock), 0, s,
+                FIR_LAUNCH_NOTE(note(), (fir1d_mfma_run_kernel<STAGE, NS, M, 1, H>), dim3(blocks), dim3(kBlock), 0, s,
                                    (const uint8_t*)x, (OutT*)y, rl, tp, nt, fr, ksp, P, bias, mode, shl, frac, hs0);
             };
             if constexpr (STAGE == FIR_OUT_U8_SAT) {
@@ -971,10 +976,10 @@ static hipError_t launch_mfma_run(const void* x, void* y, int64_t rl, int64_t tp
             }
             one(std::integral_constant<int, -1>{});
         } else if constexpr (M && MTPS == 4) {
-            hipLaunchKernelGGL((fir1d_mfma_run_kernel<STAGE, NS, M, 4>), dim3(blocks), dim3(kBlock), 0, s,
+            FIR_LAUNCH_NOTE(note(), (fir1d_mfma_run_kernel<STAGE, NS, M, 4>), dim3(blocks), dim3(kBlock), 0, s,
                                (const uint8_t*)x, (OutT*)y, rl, tp, nt, fr, ksp, P, bias, mode, shl, frac, 0);
         } else {
-            hipLaunchKernelGGL((fir1d_mfma_run_kernel<STAGE, NS, M, kMrTps>), dim3(blocks), dim3(kBlock), 0, s,
+            FIR_LAUNCH_NOTE(note(), (fir1d_mfma_run_kernel<STAGE, NS, M, kMrTps>), dim3(blocks), dim3(kBlock), 0, s,
                                (const uint8_t*)x, (OutT*)y, rl, tp, nt, fr, ksp, P, bias, mode, shl, frac, 0);
         }
     };
@@ -1008,13 +1013,13 @@ static hipError_t launch_mfma_ks(const void* x, void* y, int64_t rowlen, int64_t
     const unsigned blocks = (unsigned)(want < kMf2Blocks ? want : kMf2Blocks);
     const uint32_t sp = (uint32_t)spr, ns = (uint32_t)nsteps;
     if (fast)
-        hipLaunchKernelGGL((fir1d_mfma_step_kernel<InT, STAGE, KS, true, true>), dim3(blocks), dim3(kBlock), 0, s,
+        FIR_LAUNCH((fir1d_mfma_step_kernel<InT, STAGE, KS, true, true>), dim3(blocks), dim3(kBlock), 0, s,
                            (const InT*)x, (OutT*)y, rowlen, sp, ns, t, P, bias, 0, frac);
     else if (acc_bits == 32)
-        hipLaunchKernelGGL((fir1d_mfma_step_kernel<InT, STAGE, KS, true, false>), dim3(blocks), dim3(kBlock), 0, s,
+        FIR_LAUNCH((fir1d_mfma_step_kernel<InT, STAGE, KS, true, false>), dim3(blocks), dim3(kBlock), 0, s,
                            (const InT*)x, (OutT*)y, rowlen, sp, ns, t, P, bias, 0, frac);
     else
-        hipLaunchKernelGGL((fir1d_mfma_step_kernel<InT, STAGE, KS, false, false>), dim3(blocks), dim3(kBlock), 0, s,
+        FIR_LAUNCH((fir1d_mfma_step_kernel<InT, STAGE, KS, false, false>), dim3(blocks), dim3(kBlock), 0, s,
                            (const InT*)x, (OutT*)y, rowlen, sp, ns, t, P, bias, 32 - acc_bits, frac);
     return hipGetLastError();
 }
@@ -1039,8 +1044,9 @@ static hipError_t launch_mfma_t(const void* x, void* y, int64_t rows, int64_t ro
         if constexpr (sizeof(InT) == 1) {
             const int P16 = (hl + 15) & ~15, K16 = 32 + c + P16, KS16 = (K16 + 31) / 32;
             return launch_mfma_run<STAGE>(x, y, rl, tpr, ntiles, hq, L, P16, KS16, bias, fast, frac, acc_bits, s);
+        } else {  // (else: u8 never names the chunked kernel, so the census lists no u8 form of it)
+            return launch_mfma_long<InT, STAGE>(x, y, rl, tpr, ntiles, hq, L, P, KS, bias, fast, frac, acc_bits, s);
         }
-        return launch_mfma_long<InT, STAGE>(x, y, rl, tpr, ntiles, hq, L, P, KS, bias, fast, frac, acc_bits, s);
     }
     MfmaTaps t;
     for (int e = 0; e < 128; ++e) {

@@ -72,6 +72,14 @@ enum RegFlags : int {
     // single-image kernels keep the per-filter form (profiles/r05/pipeline_batch_ab.txt, r05ae)
     kDefer = 32768,
 };
+// The flags' names, as the launch record spells a kernel's FLAGS argument (fir_launch.h).
+inline constexpr FlagName kRegFlagNames[] = {
+    {kNtLoad, kNtLoad, "kNtLoad"},       {kNtStore, kNtStore, "kNtStore"}, {kPersist, kPersist, "kPersist"},
+    {kDot2, kDot2, "kDot2"},             {kAcc32, kAcc32, "kAcc32"},       {kU8Dot2, kU8Dot2, "kU8Dot2"},
+    {kCoal, kCoal, "kCoal"},             {kXcd, kXcd, "kXcd"},             {kU8Pk16, kU8Pk16, "kU8Pk16"},
+    {kU8PkHi8, kU8PkHi8, "kU8PkHi8"},    {kHalo, kHalo, "kHalo"},          {kEdgeDword, kEdgeDword, "kEdgeDword"},
+    {kRagged, kRagged, "kRagged"},       {kMasked, kMasked, "kMasked"},    {kDefer, kDefer, "kDefer"},
+};
 
 // One non-temporal 16-byte row-store of the coalesced path, as inline asm: the same
 // `global_store_dwordx4 ... nt` the builtin emits, but 1.6 % faster in this kernel (the compiler

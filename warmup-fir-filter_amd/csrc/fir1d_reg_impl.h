@@ -9,6 +9,7 @@
 #include "fir1d_reg.h"
 #include "fir1d_reg_launch.h"
 #include "fir_dispatch.h"
+#include "fir_launch.h"
 
 namespace fir {
 
@@ -72,7 +73,7 @@ static hipError_t launch_reg_flags(const void* x, void* y, int64_t rows, int64_t
     constexpr int FM = F == 1 && sizeof(InT) == 2 ? kMasked : 0;
     if constexpr (F == 1) {
         if (hl != nullptr || hr != nullptr) {
-            hipLaunchKernelGGL((fir1d_reg_kernel<InT, STAGE, L, CH, kRegU<InT, F>, FL | kHalo | FM, F>), dim3((unsigned)blocks),
+            FIR_LAUNCH((fir1d_reg_kernel<InT, STAGE, L, CH, kRegU<InT, F>, FL | kHalo | FM, F>), dim3((unsigned)blocks),
                                dim3(kBlock), 0, stream, (const InT*)x, (OutT*)y, g, t, 32 - acc_bits, frac, ntiles);
             return hipGetLastError();
         }
@@ -81,11 +82,11 @@ static hipError_t launch_reg_flags(const void* x, void* y, int64_t rows, int64_t
     }
     if (!g.aligned) {  // rows straddle vectors: one signal with seams patched (u8 stage), else masked
         constexpr int FX = STAGE == FIR_OUT_U8_SAT && CH == 1 ? kRagged : kMasked;
-        hipLaunchKernelGGL((fir1d_reg_kernel<InT, STAGE, L, CH, kRegU<InT, F>, FL | FX, F>), dim3((unsigned)blocks),
+        FIR_LAUNCH((fir1d_reg_kernel<InT, STAGE, L, CH, kRegU<InT, F>, FL | FX, F>), dim3((unsigned)blocks),
                            dim3(kBlock), 0, stream, (const InT*)x, (OutT*)y, g, t, 32 - acc_bits, frac, ntiles);
         return hipGetLastError();
     }
-    hipLaunchKernelGGL((fir1d_reg_kernel<InT, STAGE, L, CH, kRegU<InT, F>, FL | FM, F>), dim3((unsigned)blocks), dim3(kBlock), 0,
+    FIR_LAUNCH((fir1d_reg_kernel<InT, STAGE, L, CH, kRegU<InT, F>, FL | FM, F>), dim3((unsigned)blocks), dim3(kBlock), 0,
                        stream, (const InT*)x, (OutT*)y, g, t, 32 - acc_bits, frac, ntiles);
     return hipGetLastError();
 }
@@ -120,10 +121,10 @@ static hipError_t launch_reg_batch_flags(int n, const RegImage* im, const int32_
         const int64_t blocks = (tiles + kBlock / kWave - 1) / (kBlock / kWave);
         if (blocks == 0) return hipSuccess;
         if (ragged)  // an image whose rows straddle vectors: the deferred-store seam form (kDefer)
-            hipLaunchKernelGGL((fir1d_reg_batch_kernel<InT, STAGE, L, CH, kRegU<InT, F>, FL | kRagged | kDefer, F>),
+            FIR_LAUNCH((fir1d_reg_batch_kernel<InT, STAGE, L, CH, kRegU<InT, F>, FL | kRagged | kDefer, F>),
                                dim3((unsigned)blocks), dim3(kBlock), 0, stream, b, t, 32 - acc_bits, frac);
         else
-            hipLaunchKernelGGL((fir1d_reg_batch_kernel<InT, STAGE, L, CH, kRegU<InT, F>, FL | kRagged, F>),
+            FIR_LAUNCH((fir1d_reg_batch_kernel<InT, STAGE, L, CH, kRegU<InT, F>, FL | kRagged, F>),
                                dim3((unsigned)blocks), dim3(kBlock), 0, stream, b, t, 32 - acc_bits, frac);
         return hipGetLastError();
     }

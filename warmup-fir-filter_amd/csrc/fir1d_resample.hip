@@ -461,7 +461,7 @@ static hipError_t launch_res_np(const void* x, void* y, int64_t rows, int64_t wi
     const size_t lds = (size_t)in_dwords * sizeof(uint32_t) + res_phys(stage_bytes) + 4;
     const uint32_t magic = (1u << kResMagicShift) / (uint32_t)D + 1;
     const int64_t groups = (out_width + (int64_t)P * U - 1) / ((int64_t)P * U);
-    hipLaunchKernelGGL((fir1d_resample_kernel<InT, STAGE, CH, NP>), dim3((unsigned)(rows * groups)), dim3(kBlock), lds, s,
+    FIR_LAUNCH((fir1d_resample_kernel<InT, STAGE, CH, NP>), dim3((unsigned)(rows * groups)), dim3(kBlock), lds, s,
                        (const InT*)x, (OutT*)y, width, out_width, (uint32_t)groups, U, D, P, T, pl.S, ext, PL, magic,
                        taps, 32 - acc_bits, frac);
     return hipGetLastError();
@@ -499,11 +499,11 @@ static hipError_t launch_res_generic(const void* x, void* y, int64_t rows, int64
     if (!td) return hipErrorOutOfMemory;
     TableHold hold(td, s);
     if (needs_wide(sizeof(InT) == 1 ? FIR_IN_U8 : FIR_IN_I16, hq, L, acc_bits))
-        hipLaunchKernelGGL((fir1d_resample_generic_kernel<InT, STAGE, true>), dim3((unsigned)blocks), dim3(kBlock), 0, s,
+        FIR_LAUNCH((fir1d_resample_generic_kernel<InT, STAGE, true>), dim3((unsigned)blocks), dim3(kBlock), 0, s,
                            (const InT*)x, (OutT*)y, n_out, width, out_width, (int64_t)ch, (int64_t)U, (int64_t)D,
                            (int64_t)phase, td, L, frac, acc_bits);
     else
-        hipLaunchKernelGGL((fir1d_resample_generic_kernel<InT, STAGE, false>), dim3((unsigned)blocks), dim3(kBlock), 0, s,
+        FIR_LAUNCH((fir1d_resample_generic_kernel<InT, STAGE, false>), dim3((unsigned)blocks), dim3(kBlock), 0, s,
                            (const InT*)x, (OutT*)y, n_out, width, out_width, (int64_t)ch, (int64_t)U, (int64_t)D,
                            (int64_t)phase, td, L, frac, acc_bits);
     return hipGetLastError();

@@ -52,7 +52,6 @@ template <int R, int C, int MODE>
 static hipError_t launch_pk16_rolled(const uint8_t* x, uint8_t* y, int64_t frames, int64_t H, int64_t W,
                                      const Taps2<R, C>& t, hipStream_t s) {
     constexpr int PD = kPdPk, U = p16_lcm(R, PD + 1);
-    auto kern = fir2d_pk16_strip_kernel<R, C, PD, MODE, kMinwPk>;
     const int64_t gx = (W / 16 + kBlock - 1) / kBlock;
     int64_t rows = kPkRows;
     // whole turns of U input rows per strip (S + R - 1 a multiple of U), and at most 65535 strips
@@ -62,7 +61,7 @@ static hipError_t launch_pk16_rolled(const uint8_t* x, uint8_t* y, int64_t frame
     if ((H + rows - 1) / rows > 65535) rows = ((lo + R - 1 + U - 1) / U) * U - (R - 1);
     if (rows > H) rows = H;  // one strip: the kernel stops at its last row (t < T), not at a turn
     const int64_t nstrips = (H + rows - 1) / rows;
-    hipLaunchKernelGGL(kern, dim3((unsigned)gx, (unsigned)nstrips, (unsigned)frames), dim3(kBlock), 0, s, x, y, H, W,
+    FIR_LAUNCH((fir2d_pk16_strip_kernel<R, C, PD, MODE, kMinwPk>), dim3((unsigned)gx, (unsigned)nstrips, (unsigned)frames), dim3(kBlock), 0, s, x, y, H, W,
                        t, (int)rows);
     return hipGetLastError();
 }
@@ -196,32 +195,32 @@ static hipError_t launch2d_reg(const uint8_t* x, void* y, int64_t frames, int64_
             }
             const dim3 gpk = fir2d_reg_grid<kVec2d, kStrip2dPk>(H, W, frames);
             if (pk == (kMode2dPk16 | kMode2dPkHi8)) {
-                hipLaunchKernelGGL((fir2d_reg_kernel<R, C, STAGE, kVec2d, kStrip2dPk, SNW | kMode2dPk16 | kMode2dPkHi8, kMinwPk, kPdPk, false, true, true>),
+                FIR_LAUNCH((fir2d_reg_kernel<R, C, STAGE, kVec2d, kStrip2dPk, SNW | kMode2dPk16 | kMode2dPkHi8, kMinwPk, kPdPk, false, true, true>),
                                    gpk, dim3(kBlock), 0, s, x, (OutT*)y, H, W, t, 32 - acc_bits, frac);
                 return hipGetLastError();
             }
             if (pk == kMode2dPk16) {
-                hipLaunchKernelGGL((fir2d_reg_kernel<R, C, STAGE, kVec2d, kStrip2dPk, SNW | kMode2dPk16, kMinwPk, kPdPk, false, true, true>), gpk,
+                FIR_LAUNCH((fir2d_reg_kernel<R, C, STAGE, kVec2d, kStrip2dPk, SNW | kMode2dPk16, kMinwPk, kPdPk, false, true, true>), gpk,
                                    dim3(kBlock), 0, s, x, (OutT*)y, H, W, t, 32 - acc_bits, frac);
                 return hipGetLastError();
             }
             if (pk == (kMode2dPk16 | kMode2dPkSigned)) {
-                hipLaunchKernelGGL((fir2d_reg_kernel<R, C, STAGE, kVec2d, kStrip2dPk, SNW | kMode2dPk16 | kMode2dPkSigned, kMinwPk, kPdPk, false, true, true>),
+                FIR_LAUNCH((fir2d_reg_kernel<R, C, STAGE, kVec2d, kStrip2dPk, SNW | kMode2dPk16 | kMode2dPkSigned, kMinwPk, kPdPk, false, true, true>),
                                    gpk, dim3(kBlock), 0, s, x, (OutT*)y, H, W, t, 32 - acc_bits, frac);
                 return hipGetLastError();
             }
         }
         if (sep16 && nowrap)
-            hipLaunchKernelGGL((fir2d_reg_kernel<R, C, STAGE, kVec2d, kStrip2dSep, S16 | kMode2dNoWrap, 1, kPdSep, false, true, true>), grid,
+            FIR_LAUNCH((fir2d_reg_kernel<R, C, STAGE, kVec2d, kStrip2dSep, S16 | kMode2dNoWrap, 1, kPdSep, false, true, true>), grid,
                                dim3(kBlock), 0, s, x, (OutT*)y, H, W, t, 32 - acc_bits, frac);
         else if (sep16)
-            hipLaunchKernelGGL((fir2d_reg_kernel<R, C, STAGE, kVec2d, kStrip2dSep, S16, 1, kPdSep, false, true, true>), grid, dim3(kBlock), 0, s, x,
+            FIR_LAUNCH((fir2d_reg_kernel<R, C, STAGE, kVec2d, kStrip2dSep, S16, 1, kPdSep, false, true, true>), grid, dim3(kBlock), 0, s, x,
                                (OutT*)y, H, W, t, 32 - acc_bits, frac);
         else if (nowrap)
-            hipLaunchKernelGGL((fir2d_reg_kernel<R, C, STAGE, kVec2d, kStrip2dSep, kMode2dSep | kMode2dNoWrap, 1, kPdSep, false, true, true>), grid,
+            FIR_LAUNCH((fir2d_reg_kernel<R, C, STAGE, kVec2d, kStrip2dSep, kMode2dSep | kMode2dNoWrap, 1, kPdSep, false, true, true>), grid,
                                dim3(kBlock), 0, s, x, (OutT*)y, H, W, t, 32 - acc_bits, frac);
         else
-            hipLaunchKernelGGL((fir2d_reg_kernel<R, C, STAGE, kVec2d, kStrip2dSep, kMode2dSep, 1, kPdSep, false, true, true>), grid, dim3(kBlock), 0, s,
+            FIR_LAUNCH((fir2d_reg_kernel<R, C, STAGE, kVec2d, kStrip2dSep, kMode2dSep, 1, kPdSep, false, true, true>), grid, dim3(kBlock), 0, s,
                                x, (OutT*)y, H, W, t, 32 - acc_bits, frac);
     } else {
         // packed 16-bit pixel pairs when the whole sum provably fits 16 bits (u8 stage only)
@@ -230,27 +229,27 @@ static hipError_t launch2d_reg(const uint8_t* x, void* y, int64_t frames, int64_
             const int pk = nowrap ? plan_pk16_gen(t, hq, frac) : 0;
             const dim3 gpk = fir2d_reg_grid<kVec2dPkGen, ST>(H, W, frames);
             if (pk == (kMode2dPk16 | kMode2dPkHi8)) {
-                hipLaunchKernelGGL((fir2d_reg_kernel<R, C, STAGE, kVec2dPkGen, ST, GNW | kMode2dPkHi8, 1, PD, false, true, true>), gpk,
+                FIR_LAUNCH((fir2d_reg_kernel<R, C, STAGE, kVec2dPkGen, ST, GNW | kMode2dPkHi8, 1, PD, false, true, true>), gpk,
                                    dim3(kBlock), 0, s, x, (OutT*)y, H, W, t, 32 - acc_bits, frac);
                 return hipGetLastError();
             }
             if (pk == kMode2dPk16) {
-                hipLaunchKernelGGL((fir2d_reg_kernel<R, C, STAGE, kVec2dPkGen, ST, GNW, 1, PD, false, true, true>), gpk, dim3(kBlock), 0, s, x,
+                FIR_LAUNCH((fir2d_reg_kernel<R, C, STAGE, kVec2dPkGen, ST, GNW, 1, PD, false, true, true>), gpk, dim3(kBlock), 0, s, x,
                                    (OutT*)y, H, W, t, 32 - acc_bits, frac);
                 return hipGetLastError();
             }
             if (pk == (kMode2dPk16 | kMode2dPkSigned)) {
-                hipLaunchKernelGGL((fir2d_reg_kernel<R, C, STAGE, kVec2dPkGen, ST, GNW | kMode2dPkSigned, 1, PD, false, true, true>), gpk,
+                FIR_LAUNCH((fir2d_reg_kernel<R, C, STAGE, kVec2dPkGen, ST, GNW | kMode2dPkSigned, 1, PD, false, true, true>), gpk,
                                    dim3(kBlock), 0, s, x, (OutT*)y, H, W, t, 32 - acc_bits, frac);
                 return hipGetLastError();
             }
         }
         const dim3 grid = fir2d_reg_grid<kVec2dGen, kStrip2dGen>(H, W, frames);
         if (nowrap)
-            hipLaunchKernelGGL((fir2d_reg_kernel<R, C, STAGE, kVec2dGen, kStrip2dGen, kMode2dDot2 | kMode2dNoWrap, 4, kPdGen, false, true, true>),
+            FIR_LAUNCH((fir2d_reg_kernel<R, C, STAGE, kVec2dGen, kStrip2dGen, kMode2dDot2 | kMode2dNoWrap, 4, kPdGen, false, true, true>),
                                grid, dim3(kBlock), 0, s, x, (OutT*)y, H, W, t, 32 - acc_bits, frac);
         else
-            hipLaunchKernelGGL((fir2d_reg_kernel<R, C, STAGE, kVec2dGen, kStrip2dGen, kMode2dDot2, 4, kPdGen, false, true, true>), grid,
+            FIR_LAUNCH((fir2d_reg_kernel<R, C, STAGE, kVec2dGen, kStrip2dGen, kMode2dDot2, 4, kPdGen, false, true, true>), grid,
                                dim3(kBlock), 0, s, x, (OutT*)y, H, W, t, 32 - acc_bits, frac);
     }
     return hipGetLastError();
@@ -331,10 +330,10 @@ int launch_fir2d(const uint8_t* x, int64_t frames, int64_t H, int64_t W, const i
         with_stage(stage, [&](auto st) {
             using OutT = typename OutTraits<st>::T;
             if (wide)
-                hipLaunchKernelGGL((fir2d_generic_kernel<st, true>), grid, dim3(kBlock), 0, stream, x, (OutT*)y, H, W, td,
+                FIR_LAUNCH((fir2d_generic_kernel<st, true>), grid, dim3(kBlock), 0, stream, x, (OutT*)y, H, W, td,
                                    R, C, frac, acc_bits);
             else
-                hipLaunchKernelGGL((fir2d_generic_kernel<st, false>), grid, dim3(kBlock), 0, stream, x, (OutT*)y, H, W, td,
+                FIR_LAUNCH((fir2d_generic_kernel<st, false>), grid, dim3(kBlock), 0, stream, x, (OutT*)y, H, W, td,
                                    R, C, frac, acc_bits);
         });
         e = hipGetLastError();

@@ -337,7 +337,7 @@ static hipError_t launch_m2v(const uint8_t* x, uint8_t* y, int64_t frames, int64
     const int64_t nstrip = (H + rows - 1) / rows, nw = frames * ncol * nstrip;
     if (nw >= ((int64_t)1 << 31)) return hipErrorNotSupported;
     const unsigned blocks = (unsigned)((nw + (kBlock / kWave) - 1) / (kBlock / kWave));
-    hipLaunchKernelGGL((fir2d_mfma_kernel<R, NP, FAST, ACC32>), dim3(blocks), dim3(kBlock), 0, s, x, y, H, W,
+    FIR_LAUNCH((fir2d_mfma_kernel<R, NP, FAST, ACC32>), dim3(blocks), dim3(kBlock), 0, s, x, y, H, W,
                        (uint32_t)ncol, (uint32_t)nstrip, (uint32_t)nw, rows, t, bias, sh, 32 - acc_bits, frac);
     return hipGetLastError();
 }

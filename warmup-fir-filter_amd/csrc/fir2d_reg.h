@@ -63,6 +63,14 @@ enum Fir2dMode : int {
     kMode2dPkSigned = 32,
     kMode2dPkHi8 = 64,
 };
+// The mode's names, as the launch record spells a kernel's MODE argument (fir_launch.h): the
+// arithmetic is the VALUE of the low two bits, the rest are flags.
+inline constexpr FlagName kMode2dNames[] = {
+    {3, kMode2dMad, "mad"},           {3, kMode2dDot2, "dot2"},
+    {3, kMode2dSep, "sep"},           {kMode2dSep16, kMode2dSep16, "sep16"},
+    {kMode2dPk16, kMode2dPk16, "pk16"}, {kMode2dPkSigned, kMode2dPkSigned, "pksigned"},
+    {kMode2dPkHi8, kMode2dPkHi8, "pkhi8"}, {kMode2dNoWrap, kMode2dNoWrap, "nowrap"},
+};
 
 template <int R, int C>
 inline void pack_taps2(Taps2<R, C>& t) {

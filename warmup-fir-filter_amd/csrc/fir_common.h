@@ -8,6 +8,13 @@
 
 namespace fir {
 
+// One name of a bit-mask template argument, for the launch record (fir_launch.h): it holds when
+// (argument & mask) == value.
+struct FlagName {
+    int mask, value;
+    const char* name;
+};
+
 constexpr int kWave = 64;
 constexpr int kBlock = 256;  // 4 waves: one per SIMD of a CU
 

@@ -12,6 +12,40 @@
 
 namespace fir {
 
+// The launch record (launch_log.hip): every kernel launch of the library goes through FIR_LAUNCH,
+// which (a) lists the kernel in the census -- a registry of every instantiation any site can
+// launch, filled while the library loads by Site<K>::reg's initialiser, no launch needed -- and
+// (b) when the CALLING THREAD has the log on (fir_launch_log_begin), appends the kernel, grid and
+// block to that thread's list.  Off, a launch pays one thread-local flag test.  Names are resolved
+// only when a record is read (hipKernelNameRefByPtr + demangling).
+bool census_add(const void* kernel);
+extern thread_local bool t_launch_log_on;
+void launch_log_add(const void* kernel, dim3 grid, dim3 block, const std::string& note);
+template <auto K>
+struct Site {
+    static inline const bool reg = census_add((const void*)K);
+};
+// The record as text, one line per launch / census entry: name \t grid \t block \t flags \t note
+// (census: name \t\t\t flags \t); a bit-mask template argument (the register kernels' FLAGS, the
+// 2-D kernels' MODE) is spelled in `flags` by the tables beside the masks' definitions
+// (kRegFlagNames, kMode2dNames).  fir_status; FIR_EINVAL with *need = the bytes wanted (NUL
+// included) when cap is too small, the record kept.
+void launch_log_begin();
+int launch_log_end(char* buf, size_t cap, size_t* need, std::string* err);
+int kernel_census(char* buf, size_t cap, size_t* need, std::string* err);
+
+// FIR_LAUNCH((kernel<...>), grid, block, shmem, stream, args...): hipLaunchKernelGGL plus the
+// record.  FIR_LAUNCH_NOTE takes first a std::string expression, evaluated only when the log is
+// on, for what the kernel's form owes to run-time arguments (e.g. "mode=acc32 hs0=3").
+#define FIR_LAUNCH_NOTE(note, kernel, grid, block, shmem, stream, ...)                             \
+    do {                                                                                           \
+        (void)&::fir::Site<(kernel)>::reg;                                                         \
+        if (::fir::t_launch_log_on) ::fir::launch_log_add((const void*)(kernel), grid, block, note); \
+        hipLaunchKernelGGL(kernel, grid, block, shmem, stream, __VA_ARGS__);                       \
+    } while (0)
+#define FIR_LAUNCH(kernel, grid, block, shmem, stream, ...) \
+    FIR_LAUNCH_NOTE(std::string(), kernel, grid, block, shmem, stream, __VA_ARGS__)
+
 // Device copies of host tables (long tap sets, matrix-core tap fragments) on the current device
 // (dev_tables.hip): cached by the exact bytes they are made from -- their content, or the inputs
 // a derived table is built from, behind a kind tag (table_acquire builds the table with `fill`

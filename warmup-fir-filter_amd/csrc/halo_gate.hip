@@ -186,7 +186,7 @@ int launch_halo_mailbox_init(void* mailbox, int64_t bytes, int64_t hl_bytes, int
     if ((uintptr_t)mailbox % 128) return *err = "mailbox must be 128-byte aligned", FIR_EINVAL;
     const int64_t ndw = bytes / 4;
     const int64_t blocks = std::min<int64_t>((ndw + kBlock - 1) / kBlock, 1024);
-    hipLaunchKernelGGL(halo_mailbox_init_kernel, dim3((unsigned)blocks), dim3(kBlock), 0, stream, (uint32_t*)mailbox, ndw,
+    FIR_LAUNCH(halo_mailbox_init_kernel, dim3((unsigned)blocks), dim3(kBlock), 0, stream, (uint32_t*)mailbox, ndw,
                        (uint32_t)hl_bytes, (uint32_t)hr_bytes);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return *err = std::string("halo mailbox init launch failed: ") + hipGetErrorString(e), FIR_EHIP;
@@ -207,7 +207,7 @@ int launch_halo_gate(const void* x, int64_t seg_bytes, int64_t hl_bytes, int64_t
         return *err = "mailboxes must be 128-byte aligned", FIR_EINVAL;
     if (!(timeout_s > 0.0) || timeout_s > 600.0) return *err = "timeout_s must be in (0, 600]", FIR_EINVAL;
     const uint64_t ticks = (uint64_t)(timeout_s * 1e8);  // s_memrealtime runs at 100 MHz
-    hipLaunchKernelGGL(halo_gate_kernel, dim3(1), dim3(kWave), 0, stream, (const uint8_t*)x, seg_bytes, hl_bytes,
+    FIR_LAUNCH(halo_gate_kernel, dim3(1), dim3(kWave), 0, stream, (const uint8_t*)x, seg_bytes, hl_bytes,
                        hr_bytes, (uint32_t*)mailbox, (const uint32_t*)left_mailbox, (const uint32_t*)right_mailbox,
                        left_mailbox ? (uint8_t*)halo_left : nullptr, right_mailbox ? (uint8_t*)halo_right : nullptr,
                        status, ticks, 0u);

@@ -88,7 +88,7 @@ static hipError_t launch_ideal_reg(const uint8_t* x, double* y, int64_t rows, in
     constexpr int VEC = 4 * kIdealNV;
     const int64_t vecs = (total + VEC - 1) / VEC;
     const int aligned = rows == 1 || width % VEC == 0;
-    hipLaunchKernelGGL((fir1d_ideal_reg_kernel<L, kIdealNV, true, false, true>), dim3((unsigned)((vecs + kBlock - 1) / kBlock)),
+    FIR_LAUNCH((fir1d_ideal_reg_kernel<L, kIdealNV, true, false, true>), dim3((unsigned)((vecs + kBlock - 1) / kBlock)),
                        dim3(kBlock), 0, stream, x, y, total, (uint32_t)(rows > 1 ? width : 0), rows > 1 ? 1 : 0,
                        aligned, t);
     return hipGetLastError();
@@ -122,7 +122,7 @@ int launch_fir1d_ideal(const uint8_t* x, int64_t rows, int64_t width, const doub
     TableHold hold(td, stream);
     const int64_t blocks = (total + kIdealTile - 1) / kIdealTile;
     if (blocks >= ((int64_t)1 << 31)) return *err = "too many samples for one launch", FIR_EINVAL;
-    hipLaunchKernelGGL(fir1d_ideal_kernel, dim3((unsigned)blocks), dim3(kBlock), 0, stream, x, y, total, width,
+    FIR_LAUNCH(fir1d_ideal_kernel, dim3((unsigned)blocks), dim3(kBlock), 0, stream, x, y, total, width,
                        rows > 1 ? 1 : 0, td, L);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return *err = std::string("ideal launch failed: ") + hipGetErrorString(e), FIR_EHIP;

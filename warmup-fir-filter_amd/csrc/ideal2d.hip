@@ -212,7 +212,7 @@ static hipError_t launch_ideal2d_reg(const uint8_t* x, double* y, int64_t frames
         for (int n = 0; n < C; ++n) t.h[m][n] = h[m * C + n];
     const int64_t rows = std::max<int64_t>(kIdeal2dStrip, (H + 65534) / 65535);  // at most 65535 strips
     const int64_t gx = (W + 4 * kBlock - 1) / (4 * kBlock), gy = (H + rows - 1) / rows;
-    hipLaunchKernelGGL((fir2d_ideal_reg_kernel<R, C>), dim3((unsigned)gx, (unsigned)gy, (unsigned)frames), dim3(kBlock),
+    FIR_LAUNCH((fir2d_ideal_reg_kernel<R, C>), dim3((unsigned)gx, (unsigned)gy, (unsigned)frames), dim3(kBlock),
                        0, s, x, y, H, W, t, (int)rows);
     return hipGetLastError();
 }
@@ -250,7 +250,7 @@ int launch_fir2d_ideal(const uint8_t* x, int64_t frames, int64_t H, int64_t W, c
         if (!td) return FIR_ENOMEM;
         TableHold hold(td, stream);
         const dim3 grid((unsigned)((W + kBlock - 1) / kBlock), (unsigned)std::min<int64_t>(H, 65535), (unsigned)frames);
-        hipLaunchKernelGGL(fir2d_ideal_generic_kernel, grid, dim3(kBlock), 0, stream, x, y, H, W, td, R, C);
+        FIR_LAUNCH(fir2d_ideal_generic_kernel, grid, dim3(kBlock), 0, stream, x, y, H, W, td, R, C);
         e = hipGetLastError();
     }
     if (e != hipSuccess) return *err = std::string("ideal2d launch failed: ") + hipGetErrorString(e), FIR_EHIP;

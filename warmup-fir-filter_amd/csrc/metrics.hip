@@ -863,9 +863,9 @@ int launch_metrics_t(const double* ideal, const FT* fixed, int64_t n, double* ou
             const int slot = nb > nbf ? 1 : 0;
             const int64_t want = (nbf + kBlock / kWave - 1) / (kBlock / kWave);
             const int g = (int)(want > kMetricPBlocks ? kMetricPBlocks : want);
-            hipLaunchKernelGGL(metrics_prep<FT>, dim3(kMetricPrepBlocks), dim3(kBlock), 0, stream, ideal, fixed, n, bsum, nb,
+            FIR_LAUNCH(metrics_prep<FT>, dim3(kMetricPrepBlocks), dim3(kBlock), 0, stream, ideal, fixed, n, bsum, nb,
                                parts, parts + slot, g);
-            hipLaunchKernelGGL(metrics_leaf_kernel, dim3(g + 1), dim3(kBlock), 0, stream, ideal, fixed, bsum, nb, nbf,
+            FIR_LAUNCH(metrics_leaf_kernel, dim3(g + 1), dim3(kBlock), 0, stream, ideal, fixed, bsum, nb, nbf,
                                state, parts + slot, (const Cnt*)parts, slot + g, n, out);
             const hipError_t e = hipGetLastError();
             if (e != hipSuccess) return *err = std::string("metrics launch failed: ") + hipGetErrorString(e), FIR_EHIP;
@@ -897,20 +897,20 @@ int launch_metrics_t(const double* ideal, const FT* fixed, int64_t n, double* ou
         const int g = (int)(want > kMetricBlocks ? kMetricBlocks : want);
         const unsigned grid = (unsigned)g + (prev_hi > prev_lo ? 1u : 0u);
         if constexpr (std::is_same_v<FT, uint8_t>) {  // (not 16-byte aligned)
-            hipLaunchKernelGGL(metrics_blocks, dim3(grid), dim3(kBlock), 0, stream, ideal, fixed, bsum, nb, lo, hi,
+            FIR_LAUNCH(metrics_blocks, dim3(grid), dim3(kBlock), 0, stream, ideal, fixed, bsum, nb, lo, hi,
                                prev_lo, prev_hi, state, parts + slot);
         } else {
-            hipLaunchKernelGGL(metrics_blocks_any<FT>, dim3(grid), dim3(kBlock), 0, stream, ideal, fixed, bsum, nb, lo,
+            FIR_LAUNCH(metrics_blocks_any<FT>, dim3(grid), dim3(kBlock), 0, stream, ideal, fixed, bsum, nb, lo,
                                hi, prev_lo, prev_hi, state, parts + slot);
         }
         slot += g;
         prev_lo = lo, prev_hi = hi;
     }
     if (nb > nbf) {  // the ragged last block (its sum is the last in order)
-        hipLaunchKernelGGL(metrics_ragged<FT>, dim3(1), dim3(kBlock), 0, stream, ideal, fixed, n, bsum, nb, parts + slot);
+        FIR_LAUNCH(metrics_ragged<FT>, dim3(1), dim3(kBlock), 0, stream, ideal, fixed, n, bsum, nb, parts + slot);
         ++slot;
     }
-    hipLaunchKernelGGL(metrics_final, dim3(1), dim3(kBlock), 0, stream, (const double*)bsum, nb, prev_lo, state,
+    FIR_LAUNCH(metrics_final, dim3(1), dim3(kBlock), 0, stream, (const double*)bsum, nb, prev_lo, state,
                        (const Cnt*)parts, slot, n, out);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return *err = std::string("metrics launch failed: ") + hipGetErrorString(e), FIR_EHIP;

@@ -165,15 +165,15 @@ int launch_restore_u8(const double* a, int64_t n, int policy, uint8_t* out, void
     const int64_t waves = (n + kRestorePerWave - 1) / kRestorePerWave;
     const dim3 grid((unsigned)((waves + kBlock / kWave - 1) / (kBlock / kWave)));
     if (policy == FIR_RESTORE_CLIP) {
-        hipLaunchKernelGGL((restore_map_kernel<false>), grid, dim3(kBlock), 0, stream, a, n, out, nullptr);
+        FIR_LAUNCH((restore_map_kernel<false>), grid, dim3(kBlock), 0, stream, a, n, out, nullptr);
     } else {
         if (!work) return *err = "work must not be NULL for FIR_RESTORE_NORMALIZE", FIR_EINVAL;
         RestoreParams* pp = reinterpret_cast<RestoreParams*>(work);
         double* parts = reinterpret_cast<double*>((char*)work + 256);
         const int nb = (int)std::min<int64_t>(kRestoreBlocks, (n + kBlock - 1) / kBlock);
-        hipLaunchKernelGGL(restore_minmax_kernel, dim3(nb), dim3(kBlock), 0, stream, a, n, parts);
-        hipLaunchKernelGGL(restore_params_kernel, dim3(1), dim3(kBlock), 0, stream, parts, nb, pp);
-        hipLaunchKernelGGL((restore_map_kernel<true>), grid, dim3(kBlock), 0, stream, a, n, out, pp);
+        FIR_LAUNCH(restore_minmax_kernel, dim3(nb), dim3(kBlock), 0, stream, a, n, parts);
+        FIR_LAUNCH(restore_params_kernel, dim3(1), dim3(kBlock), 0, stream, parts, nb, pp);
+        FIR_LAUNCH((restore_map_kernel<true>), grid, dim3(kBlock), 0, stream, a, n, out, pp);
     }
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return *err = std::string("restore launch failed: ") + hipGetErrorString(e), FIR_EHIP;

@@ -16,10 +16,12 @@ Device entry points (torch tensors on a HIP device, enqueued on the current stre
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes
 import os
 import threading
 from pathlib import Path
+from typing import NamedTuple
 
 import numpy as np
 
@@ -31,7 +33,7 @@ __all__ = [
     "GATE_TIMEOUT", "GATE_LAYOUT", "build_id", "parse_devices", "METRIC_DTYPES", "fir1d_fixed_images_multi",
     "fir1d_ideal_images_multi", "host_empty", "TIMING_KEYS", "decim_out_width", "fir1d_fixed_rows_decim",
     "interp_out_width", "fir1d_fixed_rows_interp", "resample_out_width", "fir1d_fixed_rows_resample",
-    "fir1d_fixed_rows_cplx",
+    "fir1d_fixed_rows_cplx", "Launch", "launch_log", "kernel_census",
 ]
 
 IN_U8, IN_I16 = 0, 1
@@ -115,6 +117,9 @@ EXPORTS = {
     "fir_halo_mailbox_bytes": (_i64, [_i64, _i64]),
     "fir_halo_mailbox_init_dev": (_i32, [_vp, _i64, _i64, _i64, _vp]),
     "fir_halo_gate_dev": (_i32, [_vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_double, _vp]),
+    "fir_launch_log_begin": (None, []),
+    "fir_launch_log_end": (_i32, [_vp, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t)]),
+    "fir_kernel_census": (_i32, [_vp, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t)]),
 }
 
 _lib = None
@@ -246,6 +251,112 @@ def _check(rc: int, what: str) -> None:
     if rc != 0:
         msg = lib().fir_last_error().decode(errors="replace")
         raise FirHipError(f"{what} failed (status {rc}): {msg}")
+
+
+# ---- the launch record (diagnostics): which kernel instantiation a call launched -------------
+
+
+class Launch(NamedTuple):
+    """One kernel launch (or, from :func:`kernel_census`, one launchable instantiation)."""
+    kernel: str                   # the template's name without its namespace: "fir1d_reg_kernel"
+    targs: tuple                  # its template arguments as the demangled name writes them
+    flags: frozenset              # a bit-mask argument spelled out: {"kU8Dot2", "kRagged", ...}; else empty
+    grid: tuple | None            # (x, y, z) workgroups; None in the census
+    block: tuple | None
+    note: dict                    # what the form owes to run-time arguments: {"mode": "fast", "hs0": "0"}
+    name: str                     # the whole demangled name
+
+    @property
+    def inst(self) -> str:
+        """The instantiation: kernel<targs>, the census' key."""
+        return f"{self.kernel}<{', '.join(self.targs)}>" if self.targs else self.kernel
+
+
+def _split_name(name: str) -> tuple:
+    """(kernel without return type and namespaces, template arguments) of a demangled function
+    name; the arguments split at the commas of bracket depth one (they may be templates)."""
+    depth, head_end, targs, cur, start = 0, None, [], "", None
+    for i, c in enumerate(name):
+        if c in "<([":
+            if depth == 0:
+                if head_end is None:
+                    head_end = i
+                if c != "<" or start is not None or targs:
+                    break  # the parameter list: the name is over
+                start = i
+            else:
+                cur += c
+            depth += 1
+        elif c in ">)]":
+            depth -= 1
+            if depth == 0:
+                targs.append(cur.strip())
+                cur = ""
+            else:
+                cur += c
+        elif depth == 1 and c == ",":
+            targs.append(cur.strip())
+            cur = ""
+        elif depth >= 1:
+            cur += c
+    head = name if head_end is None else name[:head_end]
+    kernel = head.split()[-1].split("::")[-1] if head.split() else head
+    return kernel, tuple(targs)
+
+
+def _parse_launches(text: str) -> list:
+    out = []
+    for line in text.splitlines():
+        name, grid, block, flags, note = line.split("\t")
+        kernel, targs = _split_name(name.replace("(anonymous namespace)::", ""))
+        dims = lambda t: tuple(int(v) for v in t.split(",")) if t else None  # noqa: E731
+        out.append(Launch(kernel, targs, frozenset(f for f in flags.split("|") if f), dims(grid), dims(block),
+                          dict(kv.split("=", 1) for kv in note.split()), name))
+    return out
+
+
+def _read_record(fn, what: str) -> list:
+    need = ctypes.c_size_t(0)
+    rc = fn(None, 0, ctypes.byref(need))
+    if rc != 0 and need.value == 0:
+        _check(rc, what)
+    buf = ctypes.create_string_buffer(max(need.value, 1))
+    _check(fn(buf, len(buf), ctypes.byref(need)), what)
+    return _parse_launches(buf.value.decode())
+
+
+@contextlib.contextmanager
+def launch_log():
+    """Record the kernel launches the CALLING THREAD makes inside the block::
+
+        with fir_hip.launch_log() as log:
+            y = fir_hip.fir1d_fixed_rows(x, hq)
+        assert [l.kernel for l in log] == ["fir1d_reg_kernel"] and "kDot2" in log[0].flags
+
+    The yielded list is filled (with :class:`Launch` records, in launch order) when the block
+    ends.  Launches made by other threads (the ``devices=`` row split, fir1d_fixed_rows_sharded)
+    are not seen.  More than 4096 launches in one block raise FirHipError.  A diagnostic: off, a
+    launch pays one flag test."""
+    log: list = []
+    L = lib()
+    L.fir_launch_log_begin()
+    try:
+        yield log
+    except BaseException:
+        # the block's own exception wins: read (and so close) the log, but let no failure of that
+        # (an overflow, say) replace the error already in flight
+        try:
+            log.extend(_read_record(L.fir_launch_log_end, "fir_launch_log_end"))
+        except FirHipError:
+            pass
+        raise
+    log.extend(_read_record(L.fir_launch_log_end, "fir_launch_log_end"))
+
+
+def kernel_census() -> list:
+    """Every kernel instantiation a launch site of the library can name (:class:`Launch` records
+    without grid and block), whether or not anything ever launches it.  Needs no device."""
+    return _read_record(lib().fir_kernel_census, "fir_kernel_census")
 
 
 def device_count() -> int:
