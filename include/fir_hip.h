@@ -460,7 +460,11 @@ int fir_kernel_census(char* buf, size_t cap, size_t* need);
  *   FIR_RESTORE_CLIP       clip(rint(a), 0, 255)                         (restore_images.py:51-54)
  *   FIR_RESTORE_NORMALIZE  0 if max <= min, else rint(clip((a - min) * (255 / (max - min)),
  *                          0, 255))                                        (:57-64)
- * rint rounds half to even; NaN maps to 0.  The _dev form needs fir_restore_work_bytes() of
+ * rint rounds half to even; NaN maps to 0 (clip: that pixel; normalize: min and max are then NaN as
+ * NumPy's are, every pixel is cast(NaN), so one NaN anywhere makes the whole output 0).  An infinite
+ * max - min (an inf in the array, or a finite range that overflows) makes the scale 0 and the output
+ * 0; a subnormal max - min makes it inf, so 0 * inf = NaN -> 0 and every other pixel 255.  The _dev
+ * form needs fir_restore_work_bytes() of
  * device scratch (normalize only; may be NULL for clip); a and out 16-byte aligned. */
 typedef enum { FIR_RESTORE_CLIP = 0, FIR_RESTORE_NORMALIZE = 1 } fir_restore_policy;
 int64_t fir_restore_work_bytes(void);

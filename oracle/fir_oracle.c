@@ -156,7 +156,10 @@ int oracle_fir2d(const uint8_t* x, int64_t H, int64_t W, const int32_t* hq, int 
 }
 
 /* Reference fir_1d_ideal per row (fir_1d/model/python/fir_1d_ref.py:43-65):
- * float64, k-order, products and sums rounded separately (built with -ffp-contract=off). */
+ * float64, k-order, products and sums rounded separately (built with -ffp-contract=off).
+ * An out-of-row tap adds the term h[k] * 0.0, as include/fir_hip.h defines the entry ("zero terms
+ * for padding") and oracle/fir_oracle.py computes it: for finite h that leaves the sum as skipping
+ * the term does (the running sum is never -0.0); for an infinite or NaN h[k] the term is NaN. */
 int oracle_fir1d_ideal_rows(const uint8_t* x, int64_t rows, int64_t width, const double* h, int L,
                             double* y, int nthreads) {
     if (!x || !h || !y || L < 1) return 1;
@@ -172,10 +175,9 @@ int oracle_fir1d_ideal_rows(const uint8_t* x, int64_t rows, int64_t width, const
             double acc = 0.0;
             for (int k = 0; k < L; ++k) {
                 const int64_t idx = n - k + c;
-                if (idx >= 0 && idx < width) {
-                    volatile double t = h[k] * (double)x[r * width + idx];
-                    acc = acc + t;
-                }
+                const double xv = (idx >= 0 && idx < width) ? (double)x[r * width + idx] : 0.0;
+                volatile double t = h[k] * xv;
+                acc = acc + t;
             }
             y[r * width + n] = acc;
         }

@@ -7,7 +7,10 @@
 // rint is round-half-even (v_rndne_f64); for finite inputs rint-then-clip and
 // clip-then-rint give the same byte, so one converter serves both.  (a - lo) and the
 // product are rounded separately as in NumPy (-ffp-contract=off); the scale 255/(hi-lo)
-// is formed once on the device.  NaN maps to 0 (NumPy's cast of NaN is unspecified).
+// is formed once on the device.  NaN maps to 0 (NumPy's cast of NaN is unspecified; x86 gives 0).
+// normalize with a NaN anywhere in the array: NumPy's min / max are then NaN, `hi <= lo` is false and
+// every pixel is cast(NaN), so the whole image is 0 -- the min/max pass carries "saw a NaN" as a NaN
+// bound (fmin / fmax alone would drop it) and restore_params_kernel then sets `zero`.
 //
 // HBM layout: a wave converts 128*K consecutive doubles with whole-wave 1 KiB non-temporal
 // loads (lane-interleaved 16-byte pairs, K = 2 per lane), then transposes its result bytes
@@ -31,11 +34,16 @@ constexpr int kRestoreBlocks = 1024;
 constexpr int kRestoreLoads = 2;
 static_assert(kRestoreLoads <= 4 || kRestoreLoads % 8 == 0, "restore loads per lane");
 constexpr int kRestorePerWave = 2 * kWave * kRestoreLoads;
+constexpr int kMinmaxLoads = 4;  // 16-byte loads in flight per lane of the normalize min/max pass
 
 struct RestoreParams {
     double lo, scale;
-    int zero;  // hi <= lo: all zeros
+    int zero;  // hi <= lo, or a NaN in the array (every pixel cast(NaN) = 0): all zeros
 };
+
+// min / max that keep a NaN (np.min / np.max propagate it; fmin / fmax return the other operand)
+__device__ __forceinline__ double nan_min(double a, double b) { return a != a ? a : (b != b ? b : fmin(a, b)); }
+__device__ __forceinline__ double nan_max(double a, double b) { return a != a ? a : (b != b ? b : fmax(a, b)); }
 
 __device__ __forceinline__ uint32_t to_u8(double v) {
     if (!(v == v)) return 0u;
@@ -97,21 +105,42 @@ __global__ __launch_bounds__(kBlock) void restore_map_kernel(const double* __res
 
 __global__ __launch_bounds__(kBlock) void restore_minmax_kernel(const double* __restrict__ a, int64_t n,
                                                                 double* __restrict__ parts) {
+    typedef double d2 __attribute__((ext_vector_type(2)));
     __shared__ double smin[kBlock], smax[kBlock];
     double lo = __builtin_inf(), hi = -__builtin_inf();
-    const int64_t stride = (int64_t)gridDim.x * kBlock;
-    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += stride) {
-        const double v = a[i];
+    bool saw_nan = false;
+    auto take = [&](double v) __attribute__((always_inline)) {
         lo = fmin(lo, v);
         hi = fmax(hi, v);
+        saw_nan |= v != v;
+    };
+    // 16-byte loads (a is 16-byte aligned: launch_restore_u8), kMinmaxLoads of them in flight per
+    // lane.  With one 8-byte load per iteration the pass was bound by that load's latency, and the
+    // NaN test, a third float64 operation per sample, showed in full: 899 -> 918 us over 2^28
+    // samples; this form takes 785 us (profiles/nonfinite/README.md)
+    constexpr int U = kMinmaxLoads;
+    const d2* __restrict__ p = reinterpret_cast<const d2*>(a);
+    const int64_t pairs = n / 2, stride = (int64_t)gridDim.x * kBlock;
+    int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    for (; i + (U - 1) * stride < pairs; i += U * stride) {
+        d2 v[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) v[u] = p[i + u * stride];  // (plain loads: the map pass reads a again)
+#pragma unroll
+        for (int u = 0; u < U; ++u) take(v[u].x), take(v[u].y);
     }
-    smin[threadIdx.x] = lo;
-    smax[threadIdx.x] = hi;
+    for (; i < pairs; i += stride) {
+        const d2 v = p[i];
+        take(v.x), take(v.y);
+    }
+    if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) take(a[n - 1]);
+    smin[threadIdx.x] = saw_nan ? __builtin_nan("") : lo;
+    smax[threadIdx.x] = saw_nan ? __builtin_nan("") : hi;
     __syncthreads();
     for (int w = kBlock / 2; w > 0; w >>= 1) {
         if (threadIdx.x < w) {
-            smin[threadIdx.x] = fmin(smin[threadIdx.x], smin[threadIdx.x + w]);
-            smax[threadIdx.x] = fmax(smax[threadIdx.x], smax[threadIdx.x + w]);
+            smin[threadIdx.x] = nan_min(smin[threadIdx.x], smin[threadIdx.x + w]);
+            smax[threadIdx.x] = nan_max(smax[threadIdx.x], smax[threadIdx.x + w]);
         }
         __syncthreads();
     }
@@ -126,23 +155,23 @@ __global__ __launch_bounds__(kBlock) void restore_params_kernel(const double* __
     __shared__ double smin[kBlock], smax[kBlock];
     double lo = __builtin_inf(), hi = -__builtin_inf();
     for (int i = threadIdx.x; i < nparts; i += kBlock) {
-        lo = fmin(lo, parts[2 * i]);
-        hi = fmax(hi, parts[2 * i + 1]);
+        lo = nan_min(lo, parts[2 * i]);
+        hi = nan_max(hi, parts[2 * i + 1]);
     }
     smin[threadIdx.x] = lo;
     smax[threadIdx.x] = hi;
     __syncthreads();
     for (int w = kBlock / 2; w > 0; w >>= 1) {
         if (threadIdx.x < w) {
-            smin[threadIdx.x] = fmin(smin[threadIdx.x], smin[threadIdx.x + w]);
-            smax[threadIdx.x] = fmax(smax[threadIdx.x], smax[threadIdx.x + w]);
+            smin[threadIdx.x] = nan_min(smin[threadIdx.x], smin[threadIdx.x + w]);
+            smax[threadIdx.x] = nan_max(smax[threadIdx.x], smax[threadIdx.x + w]);
         }
         __syncthreads();
     }
     if (threadIdx.x == 0) {
         const double l = smin[0], h = smax[0];
         pp->lo = l;
-        pp->zero = !(h > l);
+        pp->zero = !(h > l);  // also when l, h are NaN (a NaN in the array)
         pp->scale = h > l ? __ddiv_rn(255.0, __dsub_rn(h, l)) : 1.0;
     }
 }
