@@ -1,0 +1,510 @@
+"""The case table and helpers of tests/test_gpu_big_index.py -- a test helper, not a test module.
+
+The 1-D kernels at sizes where a sample index passes 2^31 or 2^32, or a byte offset does, on the
+input or on the output side.  Signals of 2-4 x 10^9 samples cannot pass through the CPU oracle in
+a test's time, so the input is PERIODIC with a prime period:
+
+* one row: ``P`` frames of uniform random samples, tiled into a row of ``n`` frames.  Away from
+  the two row ends the output of every family then repeats every ``T = P * U`` output frames
+  (U = 1 where the family does not interpolate; a shift of T output frames is a shift of T * D / U
+  = P * D input frames, a whole number of periods, for any D, phase, tap count and channel count);
+* many rows: ``Q`` distinct random rows, row r of x being row r % Q of them, so output row r
+  equals output row r % Q.
+
+No power of two is a multiple of P, of Q or of Q * rowlen, so a read or a write displaced by a
+power-of-two number of elements or bytes never lands on an equal value: ``verify`` compares every
+interior period with period 1 (every row with row r % Q) on the device, which shows a displaced
+tile and, through the 0x5A sentinel the output was filled with, its untouched destination; then it
+copies back periods 0-1, the last two periods and the ragged tail (rows 0 .. Q-1 and the last Q
+rows) and compares them bit for bit with the references the other GPU tests use, run on the
+matching slice of x with a lead-in that is thrown away, which shows an error common to every
+period.
+
+Everything here works on tensors of any device: tests/test_big_index_cases.py runs the same table
+(``table(SMALL)``: every threshold 2^12, a short period) and the same ``verify`` on the CPU, the
+oracle standing in for the device, and holds ``verify`` against planted displacements.
+
+``dispatch_kernel`` restates the dispatch conditions of csrc (reg_path_ok, mfma_path_ok and the
+k-step count of launch_mfma_t, lds_path_ok, the register test of launch_fir1d_ideal,
+decim_path_ok, interp_path_ok, resample_path_ok, cplx_path_ok); ``Case.kernel`` is the kernel each
+large case was built for, and the two must agree before a case runs.
+"""
+from __future__ import annotations
+
+from dataclasses import dataclass, replace
+from typing import Callable
+
+import numpy as np
+import torch
+
+import cplx_ref
+import fir_hip
+from oracle import c_oracle
+from rate_property_cases import decim_want, interp_want, resample_want
+
+U8, I32 = fir_hip.OUT_U8_SAT, fir_hip.OUT_I32
+FRAC, ACC = 12, 32
+SENTINEL = 0x5A
+GIB = 1 << 30
+CAP_BYTES = 24 * GIB          # x + y + compare temporaries of one case
+TEMP_BYTES = 1 * GIB          # the compare temporaries' share of it
+CHUNK = 1 << 28               # elements compared at once: a bool and a uint8 temporary of 256 MiB each
+FILL = 1 << 26                # elements of the tiled block x is filled from
+
+
+@dataclass(frozen=True)
+class Scale:
+    """thr(e): the threshold that stands for 2^e; P, Q: the two prime periods; width: the row
+    length of the many-rows cases."""
+    thr: Callable[[int], int]
+    P: int
+    Q: int
+    width: int
+
+
+FULL = Scale(lambda e: 1 << e, 100_003, 1009, 4096)
+SMALL = Scale(lambda e: 1 << 12, 101, 13, 64)  # the CPU self-test: 2^12 for every threshold
+
+
+@dataclass(frozen=True)
+class Case:
+    """One call.  width: input frames per row.  x_off: elements x starts past a 16-byte boundary.
+    crosses: (side, unit, exponent) claims, e.g. ("out", "byte", 33): the output's bytes pass
+    thr(33).  kernel: the kernel the case was built for (None for a twin: whatever dispatch_kernel
+    says)."""
+    name: str
+    family: str          # fixed | bank | ideal | decim | interp | resample | cplx
+    dtype: str           # u8 | i16
+    stage: int | None    # U8 | I32; None: the float64 ideal model
+    ch: int
+    taps: int
+    width: int
+    rows: int = 1
+    up: int = 1
+    decim: int = 1
+    phase: int = 0
+    filters: int = 1
+    x_off: int = 0
+    kernel: str | None = None
+    crosses: tuple = ()
+    P: int = FULL.P
+    Q: int = FULL.Q
+
+    # ---- sizes ---------------------------------------------------------------------------------
+    @property
+    def in_itemsize(self) -> int:
+        return 1 if self.dtype == "u8" else 2
+
+    @property
+    def out_itemsize(self) -> int:
+        return 8 if self.stage is None else (4 if self.stage == I32 else 1)
+
+    @property
+    def out_width(self) -> int:
+        """Output frames per row, by the library's own host functions."""
+        if self.family == "decim":
+            return fir_hip.decim_out_width(self.width, self.decim, self.phase)
+        if self.family == "interp":
+            return fir_hip.interp_out_width(self.width, self.up)
+        if self.family == "resample":
+            return fir_hip.resample_out_width(self.width, self.up, self.decim, self.phase)
+        return self.width
+
+    @property
+    def in_elems(self) -> int:
+        return self.rows * self.width * self.ch
+
+    @property
+    def out_elems(self) -> int:
+        return self.filters * self.rows * self.out_width * self.ch
+
+    def size(self, side: str, unit: str) -> int:
+        n = self.in_elems if side == "in" else self.out_elems
+        return n * (1 if unit == "elem" else (self.in_itemsize if side == "in" else self.out_itemsize))
+
+    @property
+    def footprint(self) -> int:
+        """Device bytes of the case: x (with the slack an offset x is cut from), y, the temporaries."""
+        return (self.in_elems + 16) * self.in_itemsize + self.out_elems * self.out_itemsize + TEMP_BYTES
+
+    @property
+    def period(self) -> int:
+        """T: output frames after which a single row's output repeats."""
+        return self.P * self.up
+
+    @property
+    def torch_in(self):
+        return torch.uint8 if self.dtype == "u8" else torch.int16
+
+    @property
+    def torch_out(self):
+        return torch.float64 if self.stage is None else (torch.int32 if self.stage == I32 else torch.uint8)
+
+    @property
+    def np_in(self):
+        return np.uint8 if self.dtype == "u8" else np.int16
+
+    @property
+    def seed(self) -> int:
+        return sum(map(ord, self.name.removeprefix("twin_")))  # a twin has its case's samples and taps
+
+
+# ---- taps ------------------------------------------------------------------------------------------
+def taps_of(c: Case):
+    """The case's taps from its seed.  Real fixed taps: L ints whose sum is about U * 2^FRAC, so a
+    u8 stage spreads over its range instead of saturating (a displaced tile must not meet a row of
+    255s); bank: filters x L; ideal: L doubles; cplx: L (hr, hi) pairs."""
+    rng = np.random.default_rng(c.seed)
+    if c.family == "ideal":
+        return rng.uniform(-1.0, 1.0, c.taps)
+    if c.family == "cplx":
+        return rng.integers(-2000, 2001, (c.taps, 2))
+    h = rng.integers(50, 1200, (c.filters, c.taps)).astype(np.float64)
+    h[:, 1::3] *= -0.25  # some negative taps; the sum stays well above zero
+    h = np.rint(h * (c.up << FRAC) / h.sum(axis=1, keepdims=True)).astype(np.int64)
+    assert np.abs(h).max() <= 32639  # int16 taps the matrix-core split can hold
+    return h if c.family == "bank" else h[0]
+
+
+# ---- the case table --------------------------------------------------------------------------------
+def table(s: Scale = FULL) -> list[Case]:
+    """Every large case, each followed by its twin at offset 0 (2 P frames, or 2 Q rows)."""
+    P, Q, W, thr = s.P, s.Q, s.width, s.thr
+    pad = 3 * P + 77               # a ragged partial period and a ragged last tile
+    pad8 = (pad + 7) // 8 * 8      # ... for the kernels that need a row of whole 8-sample vectors
+    assert pad8 % 1024 != 0 and pad % 8 != 0
+
+    def up_to(n, m):
+        return -(-n // m)
+
+    big: list[Case] = []
+
+    def add(name, family, dtype, stage, ch, taps, width, **kw):
+        big.append(Case(name, family, dtype, stage, ch, taps, width, P=P, Q=Q, **kw))
+
+    # full-rate fixed, one row
+    add("fixed_u8_reg", "fixed", "u8", U8, 1, 5, thr(32) + pad, kernel="fir1d_reg_kernel",
+        crosses=(("in", "elem", 32), ("out", "elem", 32)))
+    add("fixed_i16_reg", "fixed", "i16", I32, 1, 5, thr(31) + pad, kernel="fir1d_reg_kernel",
+        crosses=(("in", "elem", 31), ("in", "byte", 32), ("out", "elem", 31), ("out", "byte", 33)))
+    add("fixed_c16_reg", "fixed", "i16", I32, 2, 3, thr(30) + pad, kernel="fir1d_reg_kernel",
+        crosses=(("in", "elem", 31), ("in", "byte", 32), ("out", "elem", 31), ("out", "byte", 33)))
+    add("fixed_u8_mfma16", "fixed", "u8", U8, 1, 16, thr(32) + pad8, kernel="fir1d_mfma_step_kernel",
+        crosses=(("in", "elem", 32), ("out", "elem", 32)))
+    add("fixed_i16_lds16", "fixed", "i16", I32, 1, 16, thr(31) + pad, kernel="fir1d_lds_kernel",
+        crosses=(("in", "elem", 31), ("in", "byte", 32), ("out", "byte", 33)))
+    add("fixed_i16_mfma48", "fixed", "i16", I32, 1, 48, thr(31) + pad8, kernel="fir1d_mfma_step_kernel",
+        crosses=(("in", "elem", 31), ("in", "byte", 32), ("out", "byte", 33)))
+    add("fixed_u8_run66", "fixed", "u8", U8, 1, 66, thr(32) + pad8, kernel="fir1d_mfma_run_kernel",
+        crosses=(("in", "elem", 32), ("out", "elem", 32)))
+    # 65 taps are three k-steps, the step kernel's last length (launch_mfma_t); the chunked kernel
+    # starts at 66, so the chunked case has 66 and the 65-tap one stays as the step kernel's edge
+    add("fixed_i16_step65", "fixed", "i16", I32, 1, 65, thr(31) + pad8, kernel="fir1d_mfma_step_kernel",
+        crosses=(("in", "elem", 31), ("in", "byte", 32), ("out", "byte", 33)))
+    add("fixed_i16_long66", "fixed", "i16", I32, 1, 66, thr(31) + pad8, kernel="fir1d_mfma_long_kernel",
+        crosses=(("in", "elem", 31), ("in", "byte", 32), ("out", "byte", 33)))
+    add("fixed_u8_generic", "fixed", "u8", U8, 1, 5, thr(32) + pad, x_off=1, kernel="fir1d_generic_kernel",
+        crosses=(("in", "elem", 32), ("out", "elem", 32)))
+
+    # full-rate fixed, many rows of W u8 samples, 5 taps
+    add("rows_u8_reg_last", "fixed", "u8", U8, 1, 5, W, rows=thr(32) // W - 1, kernel="fir1d_reg_kernel",
+        crosses=(("in", "elem", 31), ("out", "elem", 31)))           # total = 2^32 - W: the last size on it
+    add("rows_u8_reg_first_off", "fixed", "u8", U8, 1, 5, W, rows=thr(32) // W, kernel="fir1d_lds_kernel",
+        crosses=(("in", "elem", 31), ("out", "elem", 31)))           # total = 2^32: the first size off it
+    add("bank4_u8_rows", "bank", "u8", U8, 1, 5, W, rows=thr(31) // W + 3, filters=4, kernel="fir1d_reg_kernel",
+        crosses=(("in", "elem", 31), ("out", "elem", 33)))
+
+    # float64 ideal
+    add("ideal_one_row", "ideal", "u8", None, 1, 5, thr(31) + pad, kernel="fir1d_ideal_reg_kernel",
+        crosses=(("in", "elem", 31), ("out", "elem", 31), ("out", "byte", 32), ("out", "byte", 34)))
+    add("ideal_rows", "ideal", "u8", None, 1, 5, W, rows=thr(31) // W + 3, kernel="fir1d_ideal_reg_kernel",
+        crosses=(("in", "elem", 31), ("out", "byte", 34)))           # (uint32_t)g0 % rowlen32 with the top bit set
+
+    # the rate-changing and complex-tap families: the fast kernel, then the generic one (x one element off)
+    def both(name, family, kernel, *a, **kw):
+        add(name + "_fast", family, *a, kernel=kernel + "_kernel", **kw)
+        add(name + "_generic", family, *a, kernel=kernel + "_generic_kernel", x_off=1, **kw)
+
+    both("decim_u8_D2", "decim", "fir1d_decim", "u8", U8, 1, 5, thr(32) + pad, decim=2, phase=1,
+         crosses=(("in", "elem", 32), ("out", "elem", 31)))
+    both("decim_i16_D2", "decim", "fir1d_decim", "i16", I32, 1, 9, thr(32) + pad, decim=2, phase=0,
+         crosses=(("in", "elem", 32), ("in", "byte", 33), ("out", "elem", 31), ("out", "byte", 33)))
+    both("decim_c16_D3", "decim", "fir1d_decim", "i16", I32, 2, 9, thr(31) + pad, decim=3, phase=2,
+         crosses=(("in", "elem", 32), ("in", "byte", 33), ("out", "byte", 32)))
+    both("interp_u8_U16", "interp", "fir1d_interp", "u8", I32, 1, 16, thr(27) + pad, up=16,
+         crosses=(("out", "elem", 31), ("out", "byte", 33)))
+    both("interp_i16_U2", "interp", "fir1d_interp", "i16", I32, 1, 9, thr(30) + pad, up=2,
+         crosses=(("in", "byte", 31), ("out", "elem", 31), ("out", "byte", 33)))
+    both("resample_i16_3_2", "resample", "fir1d_resample", "i16", I32, 1, 72, up_to(2 * thr(31), 3) + pad, up=3,
+         decim=2, phase=1, crosses=(("out", "elem", 31), ("out", "byte", 33), ("in", "byte", 31)))
+    both("resample_u8_2_3", "resample", "fir1d_resample", "u8", U8, 1, 9, thr(32) + pad, up=2, decim=3, phase=2,
+         crosses=(("in", "elem", 32), ("out", "elem", 31)))
+    add("cplx_5_fast", "cplx", "i16", I32, 2, 5, thr(30) + pad, kernel="fir1d_cplx_kernel",
+        crosses=(("in", "elem", 31), ("in", "byte", 32), ("out", "byte", 33)))
+    add("cplx_65_generic", "cplx", "i16", I32, 2, 65, thr(30) + pad, kernel="fir1d_cplx_generic32_kernel",
+        crosses=(("in", "elem", 31), ("in", "byte", 32), ("out", "byte", 33)))
+
+    out = []
+    for c in big:
+        out.append(c)
+        small = dict(rows=2 * Q) if c.rows > 1 else dict(width=2 * P + (pad8 - pad if c.width % 8 == 0 else 0))
+        out.append(replace(c, name="twin_" + c.name, kernel=None, crosses=(), **small))
+    return out
+
+
+# ---- dispatch, restated ------------------------------------------------------------------------------
+def _mfma_ksteps(L: int) -> int:
+    c = L // 2
+    hl = L - 1 - c
+    return (32 + c + ((hl + 7) & ~7) + 31) // 32
+
+
+def dispatch_kernel(c: Case, x_ptr: int, y_ptr: int) -> str:
+    """The kernel csrc launches for the case with x and y at these addresses."""
+    u8 = c.dtype == "u8"
+    rows, ch, L = c.rows, c.ch, c.taps
+    h = np.asarray(taps_of(c) if c.family != "ideal" else [0], dtype=np.int64).reshape(-1)
+    taps16 = bool(h.min() >= -32768 and h.max() <= 32767)
+    xa = x_ptr % (8 if u8 else 16) == 0      # the alignment the LDS kernels ask of x
+    if c.family == "ideal":                   # launch_fir1d_ideal
+        total = rows * c.width
+        reg = (L <= 9 and x_ptr % 4 == 0 and y_ptr % 16 == 0 and (rows == 1 or (c.width >= 4 + L - 1 and total < 1 << 32))
+               and (total + 3) // 4 // 256 < 1 << 31)
+        return "fir1d_ideal_reg_kernel" if reg else "fir1d_ideal_kernel"
+    real_ch = ch == 1 or (ch == 2 and not u8)
+    if c.family in ("fixed", "bank"):
+        rowlen, total = c.width * ch, rows * c.width * ch
+        reg = (L <= 9 and real_ch and bool(h.min() >= -(1 << 23) and h.max() < 1 << 23) and x_ptr % 16 == 0
+               and (y_ptr % 16 == 0 or (c.family == "bank" and c.stage == U8))
+               and (rows == 1 or (rowlen >= (16 if u8 else 8) + (L - 1) * ch and total < 1 << 32)))
+        if c.family == "bank":                # launch_fir1d_rows_multi: fused u8 banks only, here
+            assert u8 and ch == 1 and reg and (c.stage == U8 or total * 4 % 16 == 0)
+            return "fir1d_reg_kernel"
+        if reg:
+            return "fir1d_reg_kernel"
+        ntiles = rows * (-(-rowlen // 1024)) if rows > 1 else -(-total // 1024)
+        mfma = (2 <= L <= 65536 and ch == 1 and bool(h.min() >= -32768 and h.max() <= 32639)
+                and (total if rows == 1 else rowlen) % 8 == 0 and xa and y_ptr % 16 == 0 and 8 <= total < 1 << 40
+                and ntiles < (1 << 32) - 2048 * 4)
+        if L >= (40 if not u8 and c.stage == I32 else 10) and mfma:
+            if _mfma_ksteps(L) <= 3:
+                return "fir1d_mfma_step_kernel"
+            return "fir1d_mfma_run_kernel" if u8 else "fir1d_mfma_long_kernel"
+        lds = (2 <= L <= 64 and ch == 1 and taps16 and (rows == 1 or rowlen % 8 == 0) and xa and y_ptr % 16 == 0
+               and total < 1 << 40)
+        return "fir1d_lds_kernel" if lds else "fir1d_generic_kernel"
+    if c.family == "cplx":                    # launch_fir1d_cplx (no case here has every hi == 0)
+        assert np.any(h.reshape(-1, 2)[:, 1] != 0)
+        dot2 = bool(h.min() >= -32767 and h.max() <= 32767)
+        if (L <= 64 and c.stage == I32 and dot2 and x_ptr % 16 == 0 and y_ptr % 16 == 0
+                and (rows == 1 or c.width % 4 == 0) and rows * c.width < 1 << 40):
+            return "fir1d_cplx_kernel"
+        return "fir1d_cplx_generic32_kernel" if x_ptr % 4 == 0 and dot2 else "fir1d_cplx_generic_kernel"
+    shape_ok = real_ch and taps16 and xa and (rows == 1 or (c.width * ch) % 8 == 0) and c.width < 1 << 40
+    if c.family == "decim":                   # decim_path_ok
+        tiles = -(-c.out_width // 512)
+        fast = 2 <= c.decim <= 16 and L <= 128 and shape_ok and tiles < 1 << 31 and rows < (1 << 31) // tiles
+        return "fir1d_decim_kernel" if fast else "fir1d_decim_generic_kernel"
+    if c.family == "interp":                  # interp_path_ok: a workgroup owns kIntInBytes / in_size input frames
+        groups = -(-c.width // (4096 // c.in_itemsize))
+        fast = 2 <= c.up <= 16 and L <= 128 and shape_ok and groups < 1 << 31 and rows < (1 << 31) // groups
+        return "fir1d_interp_kernel" if fast else "fir1d_interp_generic_kernel"
+    assert c.family == "resample" and c.up > 1 and c.decim > 1  # U = 1 or D = 1 would be forwarded
+    periods = 256                             # res_periods: kResMinT doubled up to kResInBytes of input
+    while periods * c.decim * c.in_itemsize < 4096:
+        periods *= 2
+    groups = -(-c.out_width // (periods * c.up))
+    fast = (2 <= c.up <= 16 and 2 <= c.decim <= 16 and -(-L // c.up) <= 64 and shape_ok and groups < 1 << 31
+            and rows < (1 << 31) // groups)
+    return "fir1d_resample_kernel" if fast else "fir1d_resample_generic_kernel"
+
+
+# ---- the input ---------------------------------------------------------------------------------------
+def base_of(c: Case) -> np.ndarray:
+    """The samples everything is tiled from: (1, P * ch), or (Q, width * ch) for a many-rows case."""
+    rng = np.random.default_rng(c.seed + 1)
+    lo, hi = (0, 256) if c.dtype == "u8" else (-32768, 32768)
+    shape = (c.Q, c.width * c.ch) if c.rows > 1 else (1, c.P * c.ch)
+    return rng.integers(lo, hi, shape, dtype=c.np_in)
+
+
+def make_x(c: Case, device) -> torch.Tensor:
+    """x on ``device``: a row of width * ch samples (1-D) or (rows, width * ch), filled from a tiled
+    block of whole periods, x_off elements past a 16-byte boundary."""
+    base = torch.from_numpy(base_of(c)).to(device)
+    n = c.in_elems
+    buf = torch.empty(n + 16, dtype=c.torch_in, device=device)
+    lead = (-buf.data_ptr() % 16) // c.in_itemsize + c.x_off
+    flat = buf[lead:lead + n]
+    assert flat.data_ptr() % 16 == c.x_off * c.in_itemsize
+    unit = base.numel()                                   # one period: P * ch samples, or Q rows
+    block = base.reshape(-1).repeat(max(1, FILL // unit))
+    for i in range(0, n, block.numel()):
+        m = min(block.numel(), n - i)
+        flat[i:i + m] = block[:m]
+    return flat if c.rows == 1 else flat.view(c.rows, c.width * c.ch)
+
+
+def make_y(c: Case, device) -> torch.Tensor:
+    """The output tensor of the entry's shape, every byte the sentinel."""
+    y = torch.empty(c.out_elems, dtype=c.torch_out, device=device)
+    b = y.view(torch.uint8)
+    for i in range(0, b.numel(), GIB):
+        b[i:i + GIB].fill_(SENTINEL)
+    row = (c.rows, c.out_width * c.ch) if c.rows > 1 else (c.out_width * c.ch,)
+    return y.view(((c.filters,) if c.family == "bank" else ()) + row)
+
+
+# ---- the references ------------------------------------------------------------------------------------
+def reference(c: Case, x: np.ndarray) -> np.ndarray:
+    """What the family's entry must give for the (rows, width' * ch) array x: (rows, out_width' * ch),
+    a bank (filters, rows, ...); the references of the families' own GPU tests."""
+    h = taps_of(c)
+    o = c_oracle()
+    if c.family == "fixed":
+        return o.fir1d_rows(x, h, FRAC, ACC, c.stage, channels=c.ch)
+    if c.family == "bank":
+        return np.stack([o.fir1d_rows(x, hf, FRAC, ACC, c.stage, channels=c.ch) for hf in h])
+    if c.family == "ideal":
+        return o.fir1d_ideal_rows(x, h)
+    if c.family == "decim":
+        return decim_want(x, h, c.decim, c.phase, FRAC, ACC, c.stage, c.ch).reshape(x.shape[0], -1)
+    if c.family == "interp":
+        return interp_want(x, h, c.up, FRAC, ACC, c.stage, c.ch)
+    if c.family == "resample":
+        return resample_want(x, h, c.up, c.decim, c.phase, FRAC, ACC, c.stage, c.ch)
+    return cplx_ref.want(x, h, FRAC, ACC, c.stage)
+
+
+def input_span(c: Case, out_lo: int, out_hi: int) -> tuple[int, int, int]:
+    """(lo, hi, q): the input frames [lo, hi) of a single row whose reference holds output frames
+    [out_lo, out_hi) exactly, local output m' being global output q + m'.  Output m reads the
+    stuffed signal around index m * D + phase, i.e. input frames within taps / U of it: a lead-in
+    and a lead-out of taps + D + 8 input frames cover that (or the slice ends at the row's own end,
+    where the zero padding is the true one).  lo is a multiple of D, so lo * U is one and
+    [phase::D] of the slice lines up with that of the row."""
+    U, D = c.up, c.decim
+    lead = c.taps + D + 8
+    lo = max(0, out_lo * D // U - lead)
+    lo -= lo % D
+    hi = min(c.width, -(-(out_hi * D + c.phase) // U) + lead)
+    return lo, hi, lo * U // D
+
+
+# ---- the comparisons -------------------------------------------------------------------------------------
+class Mismatch(AssertionError):
+    """verify's finding: .step ("periods" | "rows" | "band"), .index (the first differing output
+    element), .frame (its output frame, counted from the tensor's start) and .count."""
+
+    def __init__(self, c: Case, step: str, index: int, count: int, of: int, detail: str = ""):
+        self.step, self.index, self.count = step, index, count
+        self.frame = index // c.ch
+        super().__init__(f"{c.name} [{step}]: {count} of {of} compared outputs differ{detail}; the first is output "
+                         f"frame {self.frame} (element {index}, byte offset {index * c.out_itemsize:#x})")
+
+
+def _bits(t: torch.Tensor) -> torch.Tensor:
+    return t.view(torch.int64) if t.dtype == torch.float64 else t  # float64 is compared bit for bit
+
+
+def _diff(a: torch.Tensor, b: torch.Tensor) -> tuple[int, int]:
+    """(differing elements, flat index of the first in a) of a against b (broadcast); at most CHUNK
+    elements, so the temporaries are a bool and a uint8 of that many."""
+    ne = torch.ne(a, b)
+    count = int(ne.count_nonzero())
+    return (count, int(torch.argmax(ne.reshape(-1).to(torch.uint8)))) if count else (0, -1)
+
+
+def compare_periods(c: Case, y: torch.Tensor, chunk: int = CHUNK) -> None:
+    """Step 3, one row: every output frame from period 2 on, up to the row end's own edge, against
+    period 1."""
+    yb = _bits(y.reshape(-1))
+    Te = c.period * c.ch
+    edge = ((c.taps // 2 + 1) * c.up // c.decim + 2) * c.ch  # outputs that see the zero padding past the row's end
+    hi = yb.numel() - edge
+    ref = yb[Te:2 * Te]
+    count, first, m = 0, -1, max(1, chunk // Te)
+    s = 2 * Te
+    while s < hi:
+        k = min(m, (hi - s) // Te)
+        if k:
+            n, i = _diff(yb[s:s + k * Te].view(k, Te), ref)
+        else:  # the ragged last period
+            n, i = _diff(yb[s:hi], ref[:hi - s])
+        if n and first < 0:
+            first = s + i
+        count += n
+        s = s + k * Te if k else hi
+    if count:
+        raise Mismatch(c, "periods", first, count, hi - 2 * Te, f" from output frame {first // c.ch % c.period} of period 1")
+
+
+def compare_rows(c: Case, y: torch.Tensor, chunk: int = CHUNK) -> None:
+    """Step 3, many rows: every output row r >= Q against row r % Q, each plane of a bank."""
+    We = c.out_width * c.ch
+    planes = _bits(y).reshape(c.filters, c.rows, We)
+    count, first, m = 0, -1, max(1, chunk // (c.Q * We))
+    for f in range(c.filters):
+        yb = planes[f]
+        ref = yb[:c.Q]
+        r0 = c.Q
+        while r0 < c.rows:
+            k = min(m, (c.rows - r0) // c.Q)
+            if k:
+                n, i = _diff(yb[r0:r0 + k * c.Q].view(k, c.Q, We), ref)
+            else:  # the last, partial run of rows
+                n, i = _diff(yb[r0:], ref[:c.rows - r0])
+            if n and first < 0:
+                first = (f * c.rows + r0) * We + i
+            count += n
+            r0 = r0 + k * c.Q if k else c.rows
+    if count:
+        raise Mismatch(c, "rows", first, count, c.filters * max(0, c.rows - c.Q) * We,
+                       f" from row {first // We % c.rows % c.Q} of the first {c.Q}")
+
+
+def _host(t: torch.Tensor) -> np.ndarray:
+    return t.cpu().numpy()
+
+
+def _band_diff(c: Case, got: np.ndarray, want: np.ndarray, base: int, what: str) -> None:
+    """got / want: equal-shaped arrays whose flat element i is output element base + i."""
+    if got.dtype == np.float64:
+        got, want = got.view(np.int64), want.view(np.int64)
+    bad = np.flatnonzero(got.reshape(-1) != want.reshape(-1))
+    if bad.size:
+        raise Mismatch(c, "band", base + int(bad[0]), int(bad.size), got.size, f" from the reference ({what})")
+
+
+def compare_bands(c: Case, x: torch.Tensor, y: torch.Tensor) -> None:
+    """Step 4: periods 0-1 and the last two periods with the ragged tail (rows 0 .. Q-1 and the last Q
+    rows) against the reference of the matching slice of x."""
+    if c.rows > 1:
+        We = c.out_width * c.ch
+        spans = [(0, c.rows)] if c.rows <= 2 * c.Q else [(0, c.Q), (c.rows - c.Q, c.rows)]
+        y3 = y.reshape(c.filters, c.rows, We)
+        for r0, r1 in spans:
+            want = reference(c, _host(x[r0:r1])).reshape(c.filters, r1 - r0, We)
+            for f in range(c.filters):
+                _band_diff(c, _host(y3[f, r0:r1]), want[f], (f * c.rows + r0) * We, f"rows {r0} .. {r1 - 1}")
+        return
+    T, n_out = c.period, c.out_width
+    full = n_out // T
+    spans = [(0, n_out)] if full < 5 else [(0, 2 * T), ((full - 2) * T, n_out)]
+    xf, yf = x.reshape(-1), y.reshape(-1)
+    for out_lo, out_hi in spans:
+        lo, hi, q = input_span(c, out_lo, out_hi)
+        want = reference(c, _host(xf[lo * c.ch:hi * c.ch]).reshape(1, -1)).reshape(-1)
+        _band_diff(c, _host(yf[out_lo * c.ch:out_hi * c.ch]), want[(out_lo - q) * c.ch:(out_hi - q) * c.ch],
+                   out_lo * c.ch, f"output frames {out_lo} .. {out_hi - 1} from input frames {lo} .. {hi - 1}")
+
+
+def verify(c: Case, x: torch.Tensor, y: torch.Tensor, chunk: int = CHUNK) -> None:
+    """Steps 3 and 4 on the entry's output y for the input x; raises Mismatch.  The bands go first:
+    period 1 and rows 0 .. Q-1 are what step 3 compares everything else with, so an error there is
+    named where it is and not where its first copy was expected."""
+    compare_bands(c, x, y)
+    if c.rows > 1:
+        compare_rows(c, y, chunk)
+    else:
+        compare_periods(c, y, chunk)

@@ -1,0 +1,224 @@
+"""CPU self-test of tests/big_index_cases.py (the helpers of tests/test_gpu_big_index.py).
+
+The same table builder, periodic compare and band alignment run here with every threshold
+replaced by 2^12 (``table(SMALL)``, a period of 101 frames, 13 distinct rows of 64 samples) and the
+oracle standing in for the device: ``verify`` must accept the oracle's own output for every row of
+the table, and must reject a tile written to the wrong place, a tile never written, a period or a
+run of rows computed from displaced input, and a single wrong value at either end, each time naming
+the first output that differs.  The full-size table is held to what it claims: every size crosses
+the stated threshold on the stated side, every footprint is within the cap, and the dispatch
+conditions restated in ``dispatch_kernel`` (whose constants are read back from csrc) send every
+case to the kernel it was built for.
+"""
+from __future__ import annotations
+
+import re
+from pathlib import Path
+
+import numpy as np
+import pytest
+import torch
+
+import big_index_cases as bic
+from big_index_cases import FULL, SMALL, Mismatch
+
+CSRC = Path(__file__).resolve().parents[1] / "warmup-fir-filter_amd" / "csrc"
+CPU = torch.device("cpu")
+FULL_TABLE = bic.table(FULL)
+SMALL_TABLE = bic.table(SMALL)
+IDS = [c.name for c in SMALL_TABLE]
+
+
+# ---- the full-size table ---------------------------------------------------------------------------
+def test_table_is_one_table_at_two_scales():
+    assert [c.name for c in FULL_TABLE] == IDS and len(set(IDS)) == len(IDS)
+    for a, b in zip(FULL_TABLE, SMALL_TABLE):  # only the sizes differ
+        same = ("family", "dtype", "stage", "ch", "taps", "up", "decim", "phase", "filters", "x_off", "kernel", "crosses")
+        assert all(getattr(a, k) == getattr(b, k) for k in same), a.name
+    for big, twin in zip(FULL_TABLE[0::2], FULL_TABLE[1::2]):
+        assert twin.name == "twin_" + big.name and twin.kernel is None and big.kernel is not None
+        assert (twin.rows, twin.width) == ((2 * FULL.Q, big.width) if big.rows > 1 else (1, twin.width))
+        assert big.rows > 1 or 2 * FULL.P <= twin.width < 2 * FULL.P + 8
+
+
+@pytest.mark.parametrize("c", FULL_TABLE[0::2], ids=IDS[0::2])
+def test_case_crosses_what_it_claims_within_the_cap(c):
+    assert c.crosses
+    for side, unit, e in c.crosses:
+        assert c.size(side, unit) > 1 << e, (side, unit, e, c.size(side, unit))
+    assert c.footprint <= bic.CAP_BYTES, c.footprint / bic.GIB
+    if c.rows == 1:
+        # a ragged partial period, a ragged last tile of every tile size in csrc, and interior periods to compare
+        assert c.out_width % c.period != 0 and c.out_width // c.period >= 5
+        assert all(c.width % t and c.out_width % t for t in (512, 1024, 2048, 4096))
+        assert c.taps <= c.P
+    else:
+        assert c.rows % c.Q != 0 and c.rows > 2 * c.Q
+
+
+def test_the_two_register_edges_are_the_edges():
+    by = {c.name: c for c in FULL_TABLE}
+    assert by["rows_u8_reg_last"].in_elems == (1 << 32) - 4096 and by["rows_u8_reg_first_off"].in_elems == 1 << 32
+    assert by["bank4_u8_rows"].rows == (1 << 19) + 3 and by["ideal_rows"].in_elems == (1 << 31) + 3 * 4096
+
+
+@pytest.mark.parametrize("c", FULL_TABLE[0::2], ids=IDS[0::2])
+def test_dispatch_sends_the_case_to_its_kernel(c):
+    x_ptr, y_ptr = 4096 + c.x_off * c.in_itemsize, 8192  # as make_x / make_y place them
+    assert bic.dispatch_kernel(c, x_ptr, y_ptr) == c.kernel
+    if c.x_off:  # the offset is the only reason the case is off the fast kernel
+        assert bic.dispatch_kernel(c, 4096, y_ptr) != c.kernel
+
+
+def test_every_kernel_family_of_the_issue_is_in_the_table():
+    assert {c.kernel for c in FULL_TABLE[0::2]} == {
+        "fir1d_reg_kernel", "fir1d_mfma_step_kernel", "fir1d_mfma_run_kernel", "fir1d_mfma_long_kernel",
+        "fir1d_lds_kernel", "fir1d_generic_kernel", "fir1d_ideal_reg_kernel", "fir1d_decim_kernel",
+        "fir1d_decim_generic_kernel", "fir1d_interp_kernel", "fir1d_interp_generic_kernel", "fir1d_resample_kernel",
+        "fir1d_resample_generic_kernel", "fir1d_cplx_kernel", "fir1d_cplx_generic32_kernel"}
+
+
+def test_dispatch_constants_are_the_sources():
+    """The numbers dispatch_kernel restates, read back from the files that define them."""
+    want = {"fir1d.hip": {"kMfmaMinTaps": 10, "kMfmaMinTapsI32": 40}, "fir1d_lds.hip": {"kLdsMaxTaps": 64, "kLdsVec": 8},
+            "fir1d_mfma.hip": {"kMfTile": 1024, "kMfMaxTaps": 65536, "kMf2Blocks": 2048},
+            "fir1d_decim.hip": {"kDecT": 512, "kDecMaxD": 16, "kDecMaxTaps": 128},
+            "fir1d_interp.hip": {"kIntInBytes": 4096, "kIntMaxU": 16, "kIntMaxTaps": 128},
+            "fir1d_resample.hip": {"kResInBytes": 4096, "kResMinT": 256, "kResMaxUD": 16, "kResMaxPhaseTaps": 64},
+            "fir1d_cplx.hip": {"kCxMaxTaps": 64, "kCxVec": 4}, "fir_common.h": {"kBlock": 256, "kWave": 64}}
+    for name, consts in want.items():
+        text = (CSRC / name).read_text()
+        for k, v in consts.items():
+            m = re.search(rf"\b{k} = (\d+)\b", text)
+            assert m and int(m.group(1)) == v, (name, k, m and m.group(1))
+    assert "(uint32_t)g0 % g.rowlen32" in (CSRC / "fir1d_reg.h").read_text()
+    assert "(uint32_t)g0 % rowlen32" in (CSRC / "ideal_reg.h").read_text()
+    assert "total < ((int64_t)1 << 32)" in (CSRC / "fir1d.hip").read_text()
+    assert "total < ((int64_t)1 << 32)" in (CSRC / "ideal.hip").read_text()
+    assert bic._mfma_ksteps(65) == 3 and bic._mfma_ksteps(66) == 4 and bic._mfma_ksteps(16) == 2
+
+
+# ---- the oracle as the device --------------------------------------------------------------------------
+_RUNS: dict = {}
+
+
+def _oracle_run(c):
+    """(x, y) of a small-scale case, y the oracle's output over the whole of x in the entry's shape."""
+    if c.name not in _RUNS:
+        x = bic.make_x(c, CPU)
+        y = bic.make_y(c, CPU)
+        assert bool((y.view(torch.uint8) == bic.SENTINEL).all())
+        ref = bic.reference(c, x.numpy().reshape(c.rows, -1))
+        y.copy_(torch.from_numpy(np.ascontiguousarray(ref)).reshape(y.shape))
+        _RUNS[c.name] = (x, y)
+    return _RUNS[c.name]
+
+
+def _elems(y):
+    return bic._bits(y.reshape(-1))
+
+
+def _sentinel(y, lo, hi):
+    y.reshape(-1)[lo:hi].view(torch.uint8).fill_(bic.SENTINEL)
+
+
+def _first_diff(a, b) -> int:
+    d = np.flatnonzero(_elems(a).numpy() != _elems(b).numpy())
+    assert d.size, "the planted error changed nothing"
+    return int(d[0])
+
+
+def _rejects(c, x, bad, good, steps):
+    with pytest.raises(Mismatch) as e:
+        bic.verify(c, x, bad, chunk=3001)
+    first = _first_diff(bad, good)
+    assert e.value.index == first and e.value.frame == first // c.ch and e.value.step in steps, str(e.value)
+    assert f"byte offset {first * c.out_itemsize:#x}" in str(e.value) and f"frame {first // c.ch}" in str(e.value)
+
+
+@pytest.mark.parametrize("c", SMALL_TABLE, ids=IDS)
+def test_the_oracles_own_output_is_accepted(c):
+    x, y = _oracle_run(c)
+    if c.x_off:
+        assert x.data_ptr() % 16 == c.x_off * c.in_itemsize
+    if c.rows == 1:  # the input is periodic and ends in a partial period; rows repeat with Q
+        f = x.reshape(-1, c.ch)
+        assert torch.equal(f[c.P:2 * c.P], f[:c.P]) and torch.equal(f[-c.P:], f[-2 * c.P:-c.P])
+    else:
+        assert torch.equal(x[c.Q:2 * c.Q], x[:c.Q]) and not torch.equal(x[1], x[0])
+    for chunk in (bic.CHUNK, 3001, 257):  # one chunk; chunks of several periods; chunks of less than one
+        bic.verify(c, x, y, chunk=chunk)
+
+
+ONE_ROW = [c for c in SMALL_TABLE[0::2] if c.rows == 1]  # rows are compared whole
+
+
+@pytest.mark.parametrize("c", ONE_ROW, ids=[c.name for c in ONE_ROW])
+def test_band_alignment(c):
+    """Any band of a single row's output is the reference of input_span's slice, cut at q."""
+    x, y = _oracle_run(c)
+    n = c.out_width
+    for lo, hi in ((0, 1), (1, 40), (n // 3, n // 3 + 257), (n // 2 + 1, n // 2 + 2), (n - 130, n), (n - 1, n), (0, n)):
+        a, b, q = bic.input_span(c, lo, hi)
+        assert a % c.decim == 0 and 0 <= a < b <= c.width and q * c.decim == a * c.up and q <= lo
+        ref = bic.reference(c, x.reshape(-1)[a * c.ch:b * c.ch].numpy().reshape(1, -1)).reshape(-1)
+        got = y.reshape(-1)[lo * c.ch:hi * c.ch].numpy()
+        assert np.array_equal(got, ref[(lo - q) * c.ch:(hi - q) * c.ch]), (lo, hi, a, b, q)
+
+
+# one case of every family and row form (the large cases of the small-scale table), and one twin
+REJECT = [c for c in SMALL_TABLE[0::2] if c.name in (
+    "fixed_u8_reg", "fixed_c16_reg", "fixed_i16_long66", "rows_u8_reg_last", "bank4_u8_rows", "ideal_one_row", "ideal_rows",
+    "decim_c16_D3_fast", "decim_u8_D2_generic", "interp_u8_U16_fast", "resample_i16_3_2_fast", "resample_u8_2_3_generic",
+    "cplx_5_fast")]
+
+
+@pytest.mark.parametrize("c", REJECT, ids=[c.name for c in REJECT])
+def test_planted_errors_are_rejected_at_the_right_frame(c):
+    x, good = _oracle_run(c)
+    n = good.numel()
+    one_row = c.rows == 1
+    per = c.period * c.ch if one_row else c.Q * c.out_width * c.ch  # elements after which the output repeats
+    tile = (512 if n >= 16 * 512 else 128) * c.ch if one_row else 32
+    a = 2 * per + 5 * c.ch
+    shifts = [1 << k for k in (1, 4, 7, 9, 12) if a + ((1 << k) + 1) * c.ch + tile <= n - 64 * c.ch]
+    assert len(shifts) >= 3, shifts
+
+    for s in shifts:  # a tile of outputs written 2^k frames (elements, in a row form) off its place
+        d = a + s * (c.ch if one_row else 1)
+        bad = good.clone()
+        bad.reshape(-1)[d:d + tile] = good.reshape(-1)[a:a + tile]
+        _sentinel(bad, a, min(a + tile, d))  # what the misplaced write left untouched
+        _rejects(c, x, bad, good, ("periods", "rows"))
+        bad = good.clone()  # ... and the same write alone, over outputs that were right
+        bad.reshape(-1)[d:d + tile] = good.reshape(-1)[a:a + tile]
+        _rejects(c, x, bad, good, ("periods", "rows"))
+
+    bad = good.clone()  # a tile never written
+    _sentinel(bad, a + tile, a + 2 * tile)
+    _rejects(c, x, bad, good, ("periods", "rows"))
+
+    for s in (1, 8, 64):  # one period's worth of outputs (one run of Q rows) computed from x 2^k frames (rows) off
+        xs = torch.roll(x.reshape(c.rows, -1), s * (c.ch if one_row else 1), dims=1 if one_row else 0)
+        other = torch.from_numpy(np.ascontiguousarray(bic.reference(c, xs.numpy()))).reshape(good.shape)
+        bad = good.clone()
+        p = 3 * per if one_row else 2 * per
+        for f in range(c.filters):
+            o = f * (n // c.filters)
+            bad.reshape(-1)[o + p:o + p + per] = other.reshape(-1)[o + p:o + p + per]
+        _rejects(c, x, bad, good, ("periods", "rows"))
+
+    for at in (n - 1 - c.ch, 7 * c.ch + (c.ch - 1)):  # one wrong value in the last ragged tile, one in period 0
+        bad = good.clone()
+        _elems(bad)[at] ^= 1
+        _rejects(c, x, bad, good, ("band",))
+
+
+def test_a_twin_has_nothing_periodic_to_compare_and_is_still_checked():
+    c = next(c for c in SMALL_TABLE if c.name == "twin_decim_c16_D3_fast")
+    x, good = _oracle_run(c)
+    assert c.out_width < 2 * c.period
+    for at in (0, good.numel() // 2, good.numel() - 1):
+        bad = good.clone()
+        _elems(bad)[at] ^= 1
+        _rejects(c, x, bad, good, ("band",))
