@@ -24,9 +24,10 @@ Everything here works on tensors of any device: tests/test_big_index_cases.py ru
 (``table(SMALL)``: every threshold 2^12, a short period) and the same ``verify`` on the CPU, the
 oracle standing in for the device, and holds ``verify`` against planted displacements.
 
-``dispatch_kernel`` restates the dispatch conditions of csrc (reg_path_ok, mfma_path_ok and the
-k-step count of launch_mfma_t, lds_path_ok, the register test of launch_fir1d_ideal,
-decim_path_ok, interp_path_ok, resample_path_ok, cplx_path_ok); ``Case.kernel`` is the kernel each
+``dispatch_kernel`` restates the dispatch conditions of csrc (decim_path_ok, interp_path_ok,
+resample_path_ok, cplx_path_ok here; reg_path_ok, mfma_path_ok and the k-step count of
+launch_mfma_t, lds_path_ok and the register test of launch_fir1d_ideal in
+tests/fullrate_property_cases.py, which states them once); ``Case.kernel`` is the kernel each
 large case was built for, and the two must agree before a case runs.
 """
 from __future__ import annotations
@@ -40,6 +41,8 @@ import torch
 import cplx_ref
 import fir_hip
 from oracle import c_oracle
+from fullrate_property_cases import Case as FullRateCase
+from fullrate_property_cases import _mfma_ksteps, bank_fused, ideal_kernel, rows_kernel  # noqa: F401  (_mfma_ksteps: re-exported)
 from rate_property_cases import decim_want, interp_want, resample_want
 
 U8, I32 = fir_hip.OUT_U8_SAT, fir_hip.OUT_I32
@@ -253,46 +256,25 @@ def table(s: Scale = FULL) -> list[Case]:
 
 
 # ---- dispatch, restated ------------------------------------------------------------------------------
-def _mfma_ksteps(L: int) -> int:
-    c = L // 2
-    hl = L - 1 - c
-    return (32 + c + ((hl + 7) & ~7) + 31) // 32
-
-
 def dispatch_kernel(c: Case, x_ptr: int, y_ptr: int) -> str:
-    """The kernel csrc launches for the case with x and y at these addresses."""
+    """The kernel csrc launches for the case with x and y at these addresses.  The full-rate
+    (``fixed``, ``bank``) and ``ideal`` branches are tests/fullrate_property_cases.py's restatement
+    (rows_kernel, bank_fused, ideal_kernel), stated once there."""
     u8 = c.dtype == "u8"
     rows, ch, L = c.rows, c.ch, c.taps
     h = np.asarray(taps_of(c) if c.family != "ideal" else [0], dtype=np.int64).reshape(-1)
     taps16 = bool(h.min() >= -32768 and h.max() <= 32767)
     xa = x_ptr % (8 if u8 else 16) == 0      # the alignment the LDS kernels ask of x
     if c.family == "ideal":                   # launch_fir1d_ideal
-        total = rows * c.width
-        reg = (L <= 9 and x_ptr % 4 == 0 and y_ptr % 16 == 0 and (rows == 1 or (c.width >= 4 + L - 1 and total < 1 << 32))
-               and (total + 3) // 4 // 256 < 1 << 31)
-        return "fir1d_ideal_reg_kernel" if reg else "fir1d_ideal_kernel"
+        return ideal_kernel(rows, c.width, L, x_ptr, y_ptr)
     real_ch = ch == 1 or (ch == 2 and not u8)
-    if c.family in ("fixed", "bank"):
-        rowlen, total = c.width * ch, rows * c.width * ch
-        reg = (L <= 9 and real_ch and bool(h.min() >= -(1 << 23) and h.max() < 1 << 23) and x_ptr % 16 == 0
-               and (y_ptr % 16 == 0 or (c.family == "bank" and c.stage == U8))
-               and (rows == 1 or (rowlen >= (16 if u8 else 8) + (L - 1) * ch and total < 1 << 32)))
-        if c.family == "bank":                # launch_fir1d_rows_multi: fused u8 banks only, here
-            assert u8 and ch == 1 and reg and (c.stage == U8 or total * 4 % 16 == 0)
-            return "fir1d_reg_kernel"
-        if reg:
-            return "fir1d_reg_kernel"
-        ntiles = rows * (-(-rowlen // 1024)) if rows > 1 else -(-total // 1024)
-        mfma = (2 <= L <= 65536 and ch == 1 and bool(h.min() >= -32768 and h.max() <= 32639)
-                and (total if rows == 1 else rowlen) % 8 == 0 and xa and y_ptr % 16 == 0 and 8 <= total < 1 << 40
-                and ntiles < (1 << 32) - 2048 * 4)
-        if L >= (40 if not u8 and c.stage == I32 else 10) and mfma:
-            if _mfma_ksteps(L) <= 3:
-                return "fir1d_mfma_step_kernel"
-            return "fir1d_mfma_run_kernel" if u8 else "fir1d_mfma_long_kernel"
-        lds = (2 <= L <= 64 and ch == 1 and taps16 and (rows == 1 or rowlen % 8 == 0) and xa and y_ptr % 16 == 0
-               and total < 1 << 40)
-        return "fir1d_lds_kernel" if lds else "fir1d_generic_kernel"
+    if c.family == "bank":                    # launch_fir1d_rows_multi: fused u8 banks only, here
+        bank = FullRateCase("bank", "fused", c.dtype, ch, c.stage, tuple(tuple(int(v) for v in r) for r in taps_of(c)), FRAC,
+                            ACC, rows, c.width)
+        assert bank_fused(bank, x_ptr, y_ptr)
+        return "fir1d_reg_kernel"
+    if c.family == "fixed":                   # launch_fir1d_rows
+        return rows_kernel(u8, c.stage, ch, rows, c.width, [int(v) for v in h], x_ptr, y_ptr, FRAC, ACC)
     if c.family == "cplx":                    # launch_fir1d_cplx (no case here has every hi == 0)
         assert np.any(h.reshape(-1, 2)[:, 1] != 0)
         dot2 = bool(h.min() >= -32767 and h.max() <= 32767)

@@ -14,7 +14,9 @@ shrinks any failure to a small case.  Which instantiations a test actually launc
 here: tests/test_gpu_kernel_census.py holds the launched set against the library's census.
 The four rate-changing / complex families (the decimating, interpolating, resampling and
 complex-tap FIRs, their fast and generic kernels and their forwards) are
-tests/test_gpu_property_rate.py's, which also places x and y at drawn device addresses.
+tests/test_gpu_property_rate.py's, which also places x and y at drawn device addresses;
+tests/test_gpu_property_fullrate.py does the same for the device entries of the families here and
+asserts each call's route from its launch log.
 """
 from __future__ import annotations
 
