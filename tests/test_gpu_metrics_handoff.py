@@ -5,7 +5,9 @@ once by a write-through atomic store, read by returning atomics until published)
 there shows as a sum off by whole blocks (or a count off by a workgroup's), so these tests re-run the pass on the SAME output and work buffers with
 new data each time (consumer caches warm with the previous call's lines), in eager calls and in
 graph replays, at sizes with and without a ragged last block and with one to many layers of
-blocks per wave, and compare every report metric with the oracle bit for bit."""
+blocks per wave, and compare every report metric with the oracle bit for bit -- and, the stronger
+assertion on the same calls, the raw sums out[0..7] with metrics_cases.sums_ref bit for bit (the
+report's sum / n and sqrt(sum / n) hide a last-bit error of a sum in 10 % and 46 % of cases)."""
 from __future__ import annotations
 
 import numpy as np
@@ -13,6 +15,7 @@ import pytest
 import torch
 
 import fir_hip
+import metrics_cases as mc
 from fir_hip import torch_ops
 from oracle import fir_oracle as fo
 
@@ -24,6 +27,11 @@ def _case(rng, n):
     yi = rng.uniform(-64.0, 320.0, n)
     yf = np.clip(np.rint(yi) + rng.integers(-3, 4, n), 0, 255).astype(np.uint8)
     return yi, yf
+
+
+def _same_sums(sums, yi, yf, tag):
+    got, want = sums.cpu().numpy(), mc.sums_ref(yi, yf)
+    assert not mc.differing(got[:8], want) and got[8] == 0.0, (tag, mc.describe(got[:8], want), got[8])
 
 
 @pytest.mark.parametrize("n", [8192, 9 * 8192 + 4352, 1000 * 8192 + 7, 2049 * 8192, 4500 * 8192 + 100])
@@ -40,6 +48,7 @@ def test_repeated_calls_same_buffers(n):
         torch_ops.compare_metrics_dev(ideal, fixed, out=sums, work=work)
         got = fir_hip.metrics_from_sums(sums.cpu().numpy(), n)
         assert got == fo.compute_metrics(yi, yf), (n, rep)
+        _same_sums(sums, yi, yf, (n, rep))
 
 
 def test_graph_replays_new_data():
@@ -64,6 +73,7 @@ def test_graph_replays_new_data():
         g.replay()
         torch.cuda.synchronize()
         assert fir_hip.metrics_from_sums(sums.cpu().numpy(), n) == fo.compute_metrics(yi, yf), seed
+        _same_sums(sums, yi, yf, seed)
 
 
 def test_uneven_load_beside_other_streams():
@@ -88,3 +98,4 @@ def test_uneven_load_beside_other_streams():
         torch_ops.compare_metrics_dev(ideal, fixed, out=sums, work=work)
         torch.cuda.synchronize()
         assert fir_hip.metrics_from_sums(sums.cpu().numpy(), n) == fo.compute_metrics(yi, yf), rep
+        _same_sums(sums, yi, yf, rep)

@@ -99,13 +99,19 @@ def test_metrics_bit_exact_adversarial(n):
 
 
 def test_metrics_bit_exact_pipelined_parts():
-    """More than 2^25 samples: the launch is split into parts whose order-dependent chain runs
-    inside the next part's launch (metrics.hip); 2.5 parts plus a ragged block."""
+    """2.5 * 2^25 samples (10243 full blocks and a ragged one) through the host entry.  The name is
+    from round 3, when a u8 call of this size ran in parts; the host entry stages into aligned
+    buffers, so since round 4 this is the ONE-LAUNCH form (metrics_prep + metrics_leaf_kernel at
+    its full 256 streaming workgroups, ten blocks per wave), which the launch log asserts.  The
+    parts form at more than one part is tests/test_gpu_metrics_forms.py's."""
     n = 5 * (1 << 24) + 8192 * 3 + 4321
     rng = np.random.default_rng(77)
     yf = rng.integers(0, 256, n, dtype=np.uint8)
     yi = yf - rng.standard_normal(n) * np.exp2(rng.integers(-30, 31, n))
-    assert fir_hip.compare_metrics(yi, yf) == fo.compute_metrics(yi, yf)
+    with fir_hip.launch_log() as log:
+        got = fir_hip.compare_metrics(yi, yf)
+    assert [(l.kernel, l.grid[0]) for l in log] == [("metrics_prep", 64), ("metrics_leaf_kernel", 257)], [l.inst for l in log]
+    assert got == fo.compute_metrics(yi, yf)
     with pytest.raises(ValueError, match="Shape mismatch"):
         fir_hip.compare_metrics(np.zeros(3), np.zeros(4, np.uint8))
 
