@@ -1,0 +1,567 @@
+// fir1d_cplx_interp.hip — the interpolating complex-tap 1-D fixed-point FIR for complex int16:
+// zero-stuff by U, then filter with complex taps, in one polyphase pass over x itself.
+//
+//   x: rows x width frames of interleaved int16 (xr, xi); hq: L x 2 int32 (hr[k], hi[k]); c0 = L / 2
+//   out_width = width * U;  output frame j = i*U + e (0 <= e < U) meets the taps p_e + U*t only,
+//   p_e = (e + c0) mod U, c_e = (e + c0) div U, t = 0 .. n_e - 1 (n_e taps: p_e + U*t < L):
+//   re[j] = stage(round(wrap_acc( sum_t hr[p_e+U*t] * xr[i+c_e-t] - hi[p_e+U*t] * xi[i+c_e-t] )))
+//   im[j] = stage(round(wrap_acc( sum_t hr[p_e+U*t] * xi[i+c_e-t] + hi[p_e+U*t] * xr[i+c_e-t] )))
+//
+// The arithmetic is csrc/fir1d_cplx.hip's (frames outside a row are zero, one exact sum per part,
+// wrapped once, overflow-free round-half-up, int32 or saturated-u8 stage), the tiling and the LDS
+// output stage csrc/fir1d_interp.hip's.  This file is the whole device side of libfir_cinterp.so; it
+// shares the header-only device helpers of csrc/ (fir_common.h, fir_dispatch.h) and nothing compiled
+// from it or from csrc_cdecim/.
+//
+//  * fir1d_cplx_interp_kernel — the hot path (FIR_CINTERP_FAST, see route_of).  One interleaved frame
+//    is one dword, and v_dot2_i32_i16 of it against A = (hr, -hi) is the real part of one tap's
+//    product, against B = (hi, hr) the imaginary part: two v_dot2 per sub-filter tap and output frame
+//    on 32-bit wrap-around accumulators (exact mod 2^32, all the wrap to acc_bits <= 32 needs; ACC32
+//    skips the wrap).
+//
+//    Work split.  A workgroup of 256 lanes owns kCiF = 2048 consecutive input frames of ONE row
+//    (never two rows, so frames outside the row are zeroed once, at staging) and works through them
+//    as tiles of T input frames, T = 2048 halved while the tile's T * U * 8 output bytes exceed
+//    16 KiB, but not below 256 (T = 1024, 512, 512, 256 at U = 2, 3, 4, 5 and up).  A tile is computed
+//    in passes of 256 frames: lane u owns input frame u of every pass and produces its U output
+//    frames.  Grid: rows x ceil(width / 2048).
+//
+//    Input.  The workgroup stages the frames behind all of its outputs, from the 16-byte boundary at
+//    or below the first one (lead = 0..3 frames), as dwords in a LINEAR LDS window: 16-byte global
+//    loads, all of a thread's loads (at most kCiMaxIt = 3) issued before its first 16-byte LDS write.
+//    p_e and c_e depend on e alone, so the window all U phases of a frame share is frames
+//    [i + S, i + hi], S the least c_e - n_e + 1 and hi the greatest c_e: W = hi - S + 1 dwords,
+//    ceil(L / U) or one more.  The lane reads the NP >= W dwords of its frame once per pass (lane
+//    stride one dword: conflict free for ds_read_b32) and reuses them for every phase.  Every
+//    element is a whole dword, so no phase needs a v_alignbit.  Taps: per phase the sub-filter in
+//    window order, zero-padded to the bucket NP in {1, 2, 3, 4, 6, 8, 10, 12, 16, 20, 24, 28, 33}, as
+//    two packed tables passed BY VALUE (read with scalar loads at the phase's offset inside a
+//    run-time loop over e, so the registers do not depend on U): no device table, nothing
+//    allocated, so the call can be captured in a graph.  ci_slots(NP) bounds U * NP for every (L, U)
+//    that lands in a bucket: at most 176 dwords per table, 1.4 KiB of arguments.
+//
+//    Output.  The kernel is write dominated (8 U bytes out per 4 bytes in), and a lane's U output
+//    frames are 8 U bytes from the next lane's.  Every result goes to an LDS output stage instead, at
+//    the byte it has in the tile's output run, and the workgroup then writes that run as whole
+//    16-byte vectors, consecutive lanes consecutive vectors (1 KiB per store instruction).  The stage
+//    starts (y address mod 16) bytes in, so LDS vectors and global vectors line up for ANY int32 y
+//    address and row length; the partial vector at either end of a tile goes out dword by dword,
+//    inside the tile's own bytes.  Bank layout: byte b of the stage lives at b + 4 * (b / 128), one
+//    pad dword per 32.  An (re, im) pair is stored as two ds_write_b32 (y may be only 4-byte aligned,
+//    and the pad may part a pair), each with a lane stride of 2 U dwords: the 32 lanes of a write's
+//    lane group span 2 U rows of 32 dwords, 16 / U lanes per row at banks 2 U apart, and each row is
+//    one bank further on -- 2 U distinct offsets, so all 32 lanes hit distinct banks at U = 2, 4, 8
+//    and 16 (at other U at most two lanes share a bank, which a ds_write_b32 absorbs).  The read-back
+//    (four dwords per lane, lane stride four dwords, eight lanes per row) is conflict free as well.
+//
+//    LDS per workgroup: the window, (2048 + NP + 2) dwords rounded to chunks (at most 8.2 KiB), plus
+//    T * U * 8 + 16 bytes of output stage with its padding: 16.5 KiB up to U = 4 and T * U * 8 = 2 KiB
+//    * U beyond (33 KiB at U = 16): six workgroups per CU as a rule, three in the worst case.
+//
+//  * The generic kernels — every other legal call: one output frame per thread, walking the taps
+//    k = p_e, p_e + U, ... whose frame lies in the row (the in-row test as loop bounds), taps from a
+//    cached device table.  fir1d_cplx_interp_generic32_kernel (int16-sized parts, acc_bits <= 32,
+//    frac <= 31, x 4-byte aligned): 32-bit wrap-around sums, two v_dot2 per tap over a packed (A, B)
+//    table.  fir1d_cplx_interp_generic_kernel: exact 64-bit sums, or 128-bit when needs_wide says so.
+#include <cstring>
+#include <mutex>
+#include <string>
+#include <type_traits>
+#include <vector>
+
+#include "cinterp.h"
+#include "fir_common.h"
+#include "fir_dispatch.h"
+
+namespace cinterp {
+
+using fir::dot2_acc;
+using fir::IntTag;
+using fir::kBlock;
+using fir::OutTraits;
+
+constexpr int kCiF = 2048;          // input frames per workgroup: G = kCiF / T tiles
+constexpr int kCiMinT = 256;        // the smallest tile: one pass, one frame per lane
+constexpr int kCiOutBytes = 16384;  // T = kCiF halved while T * U * 8 exceeds this
+constexpr int kCiMaxU = 16;
+constexpr int kCiMaxTaps = 128;
+constexpr int kCiMaxPerPhase = 32;  // ceil(L / U) of the fast path
+constexpr int kCiMaxNP = 33;        // the largest window bucket: ceil(L / U) + 1
+constexpr int kCiChunk = 4;         // frames per staging step of one thread (16 bytes)
+
+// 16-byte chunks a workgroup stages: lead + its frames + the last frame's window (NP - 1 more)
+__host__ __device__ constexpr int ci_chunks(int lead, int frames, int NP) {
+    return (lead + frames + NP - 1 + kCiChunk - 1) / kCiChunk;
+}
+constexpr int kCiMaxIt = (ci_chunks(kCiChunk - 1, kCiF, kCiMaxNP) + kBlock - 1) / kBlock;  // staging steps per thread
+static_assert(kCiMaxIt == 3, "staging steps");
+
+// the window buckets, and the one below a bucket (0 below the first)
+constexpr int kCiBuckets[] = {1, 2, 3, 4, 6, 8, 10, 12, 16, 20, 24, 28, kCiMaxNP};
+constexpr int ci_prev_bucket(int NP) {
+    int prev = 0;
+    for (const int b : kCiBuckets) {
+        if (b >= NP) break;
+        prev = b;
+    }
+    return prev;
+}
+// Dwords per tap table of bucket NP: U * NP for the largest U that can land in it.  A window of
+// W > prev dwords has ceil(L / U) >= W - 1 >= prev, so L > U * (prev - 1) and, with L <= 128,
+// U <= 127 / (prev - 1).
+constexpr int ci_slots(int NP) {
+    const int prev = ci_prev_bucket(NP);
+    const int umax = prev < 2 || (kCiMaxTaps - 1) / (prev - 1) > kCiMaxU ? kCiMaxU : (kCiMaxTaps - 1) / (prev - 1);
+    return umax * NP;
+}
+static_assert(ci_slots(1) == 16 && ci_slots(16) == 176 && ci_slots(kCiMaxNP) == 132, "tap table sizes");
+
+// the output stage: logical byte b at b + 4 * (b / 128)
+__host__ __device__ constexpr uint32_t ci_phys(uint32_t b) { return b + ((b >> 7) << 2); }
+
+typedef uint32_t ci_u4 __attribute__((ext_vector_type(4)));
+
+template <int NP>
+struct TapsCi {
+    uint32_t a[ci_slots(NP)];  // phase e, window dword w at e * NP + w: (hr, -hi) of the tap that meets it
+    uint32_t b[ci_slots(NP)];  //                                        (hi, hr); zero where no tap does
+};
+
+template <int NP, bool ACC32>
+__global__ __launch_bounds__(kBlock) void fir1d_cplx_interp_kernel(const uint32_t* __restrict__ x,
+                                                                   int32_t* __restrict__ y, int64_t width,
+                                                                   uint32_t groups, int U, int T, int S, int PL,
+                                                                   TapsCi<NP> taps, int shl, int frac) {
+    extern __shared__ __attribute__((aligned(16))) uint32_t ci_lds[];  // PL window dwords, then the output stage
+    const uint32_t tb = blockIdx.x % groups;
+    const int64_t r = blockIdx.x / groups;
+    const int64_t i0 = (int64_t)tb * kCiF;  // first input frame of the workgroup
+    const int64_t left = width - i0;
+    const int nf = left < kCiF ? (int)left : kCiF;  // its frames (the row's last workgroup: fewer)
+    const int gt = (nf + T - 1) / T;                // its tiles
+    const int64_t a0 = i0 + S;                      // its first window's first frame (may be < 0)
+    const int64_t o = a0 & ~(int64_t)(kCiChunk - 1);  // LDS origin: floor to 4 frames
+    const int lead = (int)(a0 - o);                 // 0..3
+    const int nchunks = ci_chunks(lead, nf, NP);
+    const uint32_t* __restrict__ xr = x + r * width;
+
+    // ---- stage frames [o, o + 4 * nchunks) of the row (zero outside [0, width)): first every load
+    // of the thread, then the LDS writes
+    ci_u4 raw[kCiMaxIt];
+#pragma unroll
+    for (int it = 0; it < kCiMaxIt; ++it) {
+        const int k = threadIdx.x + it * kBlock;
+        if (k >= nchunks) break;
+        const int64_t f = o + (int64_t)k * kCiChunk;
+        if (f >= 0 && f + kCiChunk <= width) {
+            raw[it] = *reinterpret_cast<const ci_u4*>(xr + f);
+        } else {  // a chunk that crosses a row end, or lies outside the row
+            raw[it].x = f >= 0 && f < width ? xr[f] : 0u;
+            raw[it].y = f + 1 >= 0 && f + 1 < width ? xr[f + 1] : 0u;
+            raw[it].z = f + 2 >= 0 && f + 2 < width ? xr[f + 2] : 0u;
+            raw[it].w = f + 3 >= 0 && f + 3 < width ? xr[f + 3] : 0u;
+        }
+    }
+#pragma unroll
+    for (int it = 0; it < kCiMaxIt; ++it) {
+        const int k = threadIdx.x + it * kBlock;
+        if (k >= nchunks) break;
+        *reinterpret_cast<ci_u4*>(ci_lds + kCiChunk * k) = raw[it];
+    }
+    __syncthreads();
+
+    uint32_t* const outw = ci_lds + PL;
+    const int u = threadIdx.x;
+    const int64_t out_width = width * U;
+    const uint32_t fstep = (uint32_t)U * 8u;  // bytes from an input frame's outputs to the next frame's
+    for (int g = 0; g < gt; ++g) {
+        const int64_t ig = i0 + (int64_t)g * T;                 // the tile's first input frame
+        const int nv = width - ig < T ? (int)(width - ig) : T;  // its frames inside the row
+        char* const yt = reinterpret_cast<char*>(y + (r * out_width + ig * U) * 2);
+        const uint32_t sh = (uint32_t)(reinterpret_cast<uintptr_t>(yt) & 15u);  // the stage's first byte
+
+        // ---- lane u: the U output frames of input frame u of every pass (kBlock frames), into the stage
+        for (int fp = u; fp < nv; fp += kBlock) {
+            uint32_t d[NP];
+            const int wb = lead + g * T + fp;
+#pragma unroll
+            for (int w = 0; w < NP; ++w) d[w] = ci_lds[wb + w];
+            uint32_t b = sh + (uint32_t)fp * fstep;  // frame fp, phase 0
+            for (int e = 0; e < U; ++e, b += 8u) {
+                const uint32_t* __restrict__ ta = taps.a + e * NP;  // wave-uniform
+                const uint32_t* __restrict__ tq = taps.b + e * NP;
+                uint32_t re = 0, im = 0;
+                // at most 16 window dwords at a time, so that a phase's 2 NP tap dwords are never
+                // all live in SGPRs at once (66 of them at NP = 33 spilled)
+                constexpr int NC = (NP + 15) / 16, CW = (NP + NC - 1) / NC;
+#pragma unroll
+                for (int c = 0; c < NC; ++c) {
+                    if (c) __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                    for (int w = c * CW; w < (c + 1) * CW && w < NP; ++w) {
+                        re = dot2_acc(d[w], ta[w], re);
+                        im = dot2_acc(d[w], tq[w], im);
+                    }
+                }
+                outw[ci_phys(b) >> 2] = (uint32_t)fir::round_acc<ACC32>(re, shl, frac);
+                outw[ci_phys(b + 4u) >> 2] = (uint32_t)fir::round_acc<ACC32>(im, shl, frac);
+            }
+        }
+        __syncthreads();
+
+        // ---- the tile's output run [sh, end) of the stage, as 16-byte vectors at 16-byte addresses
+        const uint32_t end = sh + (uint32_t)nv * fstep;
+        const uint32_t nvec = (end + 15u) >> 4;
+        for (uint32_t v = threadIdx.x; v < nvec; v += kBlock) {
+            const uint32_t lo = 16u * v;
+            if (lo >= sh && lo + 16u <= end) {
+                ci_u4 q;
+                q.x = outw[ci_phys(lo) >> 2];
+                q.y = outw[ci_phys(lo + 4) >> 2];
+                q.z = outw[ci_phys(lo + 8) >> 2];
+                q.w = outw[ci_phys(lo + 12) >> 2];
+                *reinterpret_cast<ci_u4*>(yt - sh + lo) = q;
+            } else {  // the partial vector at either end of the run
+                const uint32_t b0 = lo < sh ? sh : lo, b1 = lo + 16u < end ? lo + 16u : end;
+                for (uint32_t b = b0; b < b1; b += 4u) *reinterpret_cast<uint32_t*>(yt - sh + b) = outw[ci_phys(b) >> 2];
+            }
+        }
+        __syncthreads();  // the next tile overwrites the stage
+    }
+}
+
+// One output frame per thread: frame gi = r * out_width + i * U + e sums the taps p_e + U * t whose
+// frame i + c_e - t lies in row r; taps[2k] = hr[k], taps[2k + 1] = hi[k].
+template <int STAGE, bool WIDE>
+__global__ __launch_bounds__(kBlock) void fir1d_cplx_interp_generic_kernel(const int16_t* __restrict__ x,
+                                                                           typename OutTraits<STAGE>::T* __restrict__ y,
+                                                                           int64_t n_out, int64_t width, int64_t U,
+                                                                           const int32_t* __restrict__ taps, int L,
+                                                                           int frac, int acc_bits) {
+    const int64_t gi = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (gi >= n_out) return;
+    const int64_t out_width = width * U;
+    const int64_t j = gi % out_width, r = gi / out_width;
+    const int64_t i = j / U, e = j % U;
+    const int64_t pe = (e + L / 2) % U, n = i + (e + L / 2) / U;  // tap pe + U * t reads frame n - t
+    // 0 <= n - t < width  <=>  n - width < t <= n;  pe + U * t <= L - 1
+    const int64_t t_lo = n - width + 1 > 0 ? n - width + 1 : 0;
+    const int64_t t_max = pe < L ? (L - 1 - pe) / U : -1;
+    const int64_t t_hi = n < t_max ? n : t_max;
+    const int16_t* __restrict__ xr = x + 2 * r * width;
+    using Acc = typename std::conditional<WIDE, unsigned __int128, uint64_t>::type;
+    using SAcc = typename std::conditional<WIDE, __int128, int64_t>::type;
+    Acc re = 0, im = 0;
+    for (int64_t t = t_lo; t <= t_hi; ++t) {
+        const int64_t k = pe + U * t;
+        const int64_t hr = taps[2 * k], hi = taps[2 * k + 1];
+        const int64_t f = n - t;
+        const int64_t ar = xr[2 * f], ai = xr[2 * f + 1];
+        re += (Acc)(SAcc)(hr * ar) - (Acc)(SAcc)(hi * ai);
+        im += (Acc)(SAcc)(hr * ai) + (Acc)(SAcc)(hi * ar);
+    }
+    if constexpr (WIDE) {
+        y[2 * gi] = fir::stage_out128<STAGE>(fir::round128((__int128)re, frac, acc_bits));
+        y[2 * gi + 1] = fir::stage_out128<STAGE>(fir::round128((__int128)im, frac, acc_bits));
+    } else {
+        y[2 * gi] = fir::stage_out<STAGE>(fir::round64((int64_t)re, frac, acc_bits));
+        y[2 * gi + 1] = fir::stage_out<STAGE>(fir::round64((int64_t)im, frac, acc_bits));
+    }
+}
+
+// The same walk on 32-bit wrap-around accumulators: pk[2k] = (hr[k], -hi[k]), pk[2k + 1] =
+// (hi[k], hr[k]), two v_dot2_i32_i16 per tap; a frame is one aligned dword.
+template <int STAGE>
+__global__ __launch_bounds__(kBlock) void fir1d_cplx_interp_generic32_kernel(
+    const uint32_t* __restrict__ x, typename OutTraits<STAGE>::T* __restrict__ y, int64_t n_out, int64_t width, int64_t U,
+    const uint32_t* __restrict__ pk, int L, int shl, int frac) {
+    const int64_t gi = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (gi >= n_out) return;
+    const int64_t out_width = width * U;
+    const int64_t j = gi % out_width, r = gi / out_width;
+    const int64_t i = j / U, e = j % U;
+    const int64_t pe = (e + L / 2) % U, n = i + (e + L / 2) / U;
+    const int64_t t_lo = n - width + 1 > 0 ? n - width + 1 : 0;
+    const int64_t t_max = pe < L ? (L - 1 - pe) / U : -1;
+    const int64_t t_hi = n < t_max ? n : t_max;
+    const uint32_t* __restrict__ xf = x + r * width + n;  // tap pe + U * t meets frame xf[-t]
+    uint32_t re = 0, im = 0;
+    for (int64_t t = t_lo; t <= t_hi; ++t) {
+        const uint32_t d = xf[-t];
+        const int64_t k = pe + U * t;
+        re = dot2_acc(d, pk[2 * k], re);
+        im = dot2_acc(d, pk[2 * k + 1], im);
+    }
+    y[2 * gi] = fir::stage_out32<STAGE>(fir::round32(re, shl, frac));
+    y[2 * gi + 1] = fir::stage_out32<STAGE>(fir::round32(im, shl, frac));
+}
+
+// ---------------------------------------------------------------------------------------
+// Host side.
+
+int64_t out_width(int64_t width, int up) {
+    int64_t ow = 0;
+    if (width < 0 || up < 1 || __builtin_mul_overflow(width, (int64_t)up, &ow)) return -1;
+    return ow;
+}
+
+// csrc/fir1d.hip's check_fir1d for int16 of two channels and one filter, its order and its texts
+// (tests/test_cabi_cinterp.py holds them against libfir_hip.so's), then the header's checks 2 to 4.
+int check(const void* x, const void* y, int64_t rows, int64_t width, const int32_t* hq, int L, int up, int frac,
+          int acc_bits, int stage, std::string* err) {
+    if (stage != FIR_OUT_U8_SAT && stage != FIR_OUT_I32)
+        return *err = "out_stage must be FIR_OUT_U8_SAT or FIR_OUT_I32", FIR_EINVAL;
+    if (rows < 0 || width < 0) return *err = "rows and width must be >= 0", FIR_EINVAL;
+    if (!hq) return *err = "hq must not be NULL", FIR_EINVAL;
+    if (L < 1 || L > FIR_MAX_TAPS) return *err = "taps must be in [1, " + std::to_string(FIR_MAX_TAPS) + "]", FIR_EINVAL;
+    if (frac < 1 || acc_bits < 1) return *err = "frac_bits and acc_bits must be >= 1", FIR_EINVAL;
+    if (up < 1) return *err = "up must be >= 1", FIR_EINVAL;
+    int64_t rw = 0, n = 0;
+    if (__builtin_mul_overflow(rows, width, &rw) || __builtin_mul_overflow(rw, (int64_t)up, &n) || n > INT64_MAX / 8)
+        return *err = "rows * width * up * 2 * 4 bytes must fit in int64", FIR_EINVAL;
+    if (rows != 0 && width != 0 && (!x || !y)) return *err = "x and y must not be NULL", FIR_EINVAL;
+    return FIR_OK;
+}
+
+// 32-bit wrap-around sums over v_dot2_i32_i16 are exact for the call: both tap parts (and -hi) fit
+// in int16, and the wrap and the rounding shift stay inside 32 bits
+static bool dot2_ok(const int32_t* hq, int L, int frac, int acc_bits) {
+    if (acc_bits > 32 || frac > 31) return false;
+    for (int64_t k = 0; k < 2 * (int64_t)L; ++k)
+        if (hq[k] < -32767 || hq[k] > 32767) return false;
+    return true;
+}
+
+// csrc/fir1d.hip's needs_wide for int16 samples over the 2 L tap parts: a no-wrap call whose exact
+// sum could reach 2^63
+static bool needs_wide(const int32_t* hq, int L, int acc_bits) {
+    if (acc_bits < 64) return false;
+    unsigned __int128 habs = 0;
+    for (int64_t k = 0; k < 2 * (int64_t)L; ++k) habs += (unsigned __int128)(hq[k] < 0 ? -(int64_t)hq[k] : (int64_t)hq[k]);
+    return habs * 32768 >= ((unsigned __int128)1 << 63);
+}
+
+// The window all U phases share: *S its first frame relative to the output's input frame, returns
+// its dwords W = hi - S + 1 (the header's "window").
+static int window_of(int L, int U, int* S) {
+    int lo = 0, hi = 0;
+    bool any = false;
+    for (int e = 0; e < U; ++e) {
+        const int pe = (e + L / 2) % U, ce = (e + L / 2) / U;
+        if (pe >= L) continue;  // an empty phase: its outputs are 0
+        const int ne = (L - pe + U - 1) / U;
+        if (!any || ce - ne + 1 < lo) lo = ce - ne + 1;
+        if (!any || ce > hi) hi = ce;
+        any = true;
+    }
+    *S = lo;
+    return hi - lo + 1;
+}
+
+static int bucket_of(int W) {
+    for (const int b : kCiBuckets)
+        if (W <= b) return b;
+    return kCiMaxNP;
+}
+
+// input frames per tile: the workgroup's frames, halved while the tile's outputs exceed kCiOutBytes
+static int tile_of(int U) {
+    int T = kCiF;
+    while (T > kCiMinT && T * U * 8 > kCiOutBytes) T /= 2;
+    return T;
+}
+
+int route_of(uintptr_t x, uintptr_t y, int64_t rows, int64_t width, const int32_t* hq, int L, int up, int frac,
+             int acc_bits, int stage, int* bucket) {
+    (void)y;  // y may sit at any element address on every route
+    *bucket = 0;
+    const bool d2 = dot2_ok(hq, L, frac, acc_bits);
+    if (d2 && up >= 2 && up <= kCiMaxU && L <= kCiMaxTaps && (L + up - 1) / up <= kCiMaxPerPhase &&
+        stage == FIR_OUT_I32 && x % 16 == 0 && (rows == 1 || width % kCiChunk == 0)) {  // every row starts as x does
+        const int64_t groups = (width + kCiF - 1) / kCiF;
+        // the grid is rows * groups < 2^31 workgroups; the kernel holds a group index in 32 bits
+        if (width < ((int64_t)1 << 40) && rows <= (((int64_t)1 << 31) - 1) / groups) {
+            int S = 0;
+            *bucket = bucket_of(window_of(L, up, &S));
+            return FIR_CINTERP_FAST;
+        }
+    }
+    if (d2 && x % 4 == 0) return FIR_CINTERP_GENERIC32;
+    return needs_wide(hq, L, acc_bits) ? FIR_CINTERP_GENERIC128 : FIR_CINTERP_GENERIC64;
+}
+
+// ---- the launch wrapper: every kernel of the library is launched here, and what was launched is
+// kept for last_launch (this thread)
+thread_local int t_route = FIR_CINTERP_NONE, t_bucket = 0;
+
+template <typename... KArgs, typename... Args>
+static hipError_t launch_recorded(int route, int bucket, void (*kernel)(KArgs...), dim3 grid, size_t shmem,
+                                  hipStream_t s, Args... args) {
+    hipLaunchKernelGGL(kernel, grid, dim3(kBlock), shmem, s, (KArgs)args...);
+    const hipError_t e = hipGetLastError();
+    if (e == hipSuccess) {
+        t_route = route;
+        t_bucket = bucket;
+    }
+    return e;
+}
+
+void last_launch(int* route, int* bucket) {
+    if (route) *route = t_route;
+    if (bucket) *bucket = t_bucket;
+}
+
+// ---- the generic kernels' tap tables: device copies cached per device by the exact bytes they
+// hold, confirmed by comparing them, uploaded once (complete before the call returns).  A caller
+// holds g_tab_mu from the lookup until its launch is enqueued, so when the cached bytes of a
+// device pass kTabCap a device-wide synchronise leaves no launch that reads a table outstanding
+// and the device's tables are freed; a table used inside a stream capture is never freed (the
+// graph may replay it), and nothing is evicted while a capture is under way.
+constexpr size_t kTabCap = size_t(64) << 20;
+struct Table {
+    int dev;
+    std::vector<uint8_t> key;
+    void* d;
+    bool pinned;
+};
+static std::mutex g_tab_mu;
+static std::vector<Table> g_tabs;
+
+static const void* table_locked(const void* host, size_t bytes, hipStream_t s, hipError_t* e) {
+    int dev = 0;
+    if ((*e = hipGetDevice(&dev)) != hipSuccess) return nullptr;
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    const bool capturing = hipStreamIsCapturing(s, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone;
+    size_t held = 0;
+    for (Table& t : g_tabs) {
+        if (t.dev != dev) continue;
+        if (t.key.size() == bytes && std::memcmp(t.key.data(), host, bytes) == 0) {
+            t.pinned |= capturing;
+            return t.d;
+        }
+        held += t.key.size();
+    }
+    if (held && held + bytes > kTabCap && !capturing && hipDeviceSynchronize() == hipSuccess) {
+        for (size_t i = g_tabs.size(); i-- > 0;)
+            if (g_tabs[i].dev == dev && !g_tabs[i].pinned) {
+                (void)hipFree(g_tabs[i].d);
+                g_tabs.erase(g_tabs.begin() + (ptrdiff_t)i);
+            }
+    }
+    void* d = nullptr;
+    if ((*e = hipMalloc(&d, bytes)) != hipSuccess) return nullptr;
+    if ((*e = hipMemcpy(d, host, bytes, hipMemcpyHostToDevice)) != hipSuccess) {
+        (void)hipFree(d);
+        return nullptr;
+    }
+    const uint8_t* hb = (const uint8_t*)host;
+    g_tabs.push_back(Table{dev, std::vector<uint8_t>(hb, hb + bytes), d, false});
+    return d;
+}
+
+template <int NP>
+static hipError_t launch_fast_np(const void* x, void* y, int64_t rows, int64_t width, const int32_t* hq, int L, int U,
+                                 int S, int frac, int acc_bits, hipStream_t s) {
+    if (U * NP > ci_slots(NP)) return hipErrorInvalidValue;  // ci_slots' bound: never taken
+    TapsCi<NP> t = {};
+    for (int e = 0; e < U; ++e) {
+        const int pe = (e + L / 2) % U, ce = (e + L / 2) / U;
+        const int ne = pe < L ? (L - pe + U - 1) / U : 0;
+        for (int w = 0; w < NP; ++w) {  // window dword w is frame S + w: tap t = ce - S - w of the phase
+            const int tt = ce - S - w;
+            if (tt < 0 || tt >= ne) continue;
+            const int32_t hr = hq[2 * (pe + U * tt)], hi = hq[2 * (pe + U * tt) + 1];
+            const uint32_t r16 = (uint32_t)hr & 0xFFFFu, i16 = (uint32_t)hi & 0xFFFFu, ni16 = (uint32_t)(-hi) & 0xFFFFu;
+            t.a[e * NP + w] = r16 | (ni16 << 16);
+            t.b[e * NP + w] = i16 | (r16 << 16);
+        }
+    }
+    const int T = tile_of(U);
+    const int PL = ci_chunks(kCiChunk - 1, kCiF, NP) * kCiChunk;  // window dwords (lead <= 3)
+    const uint32_t stage_bytes = (uint32_t)(T * U * 8) + 16u;
+    const size_t lds = (size_t)PL * sizeof(uint32_t) + ci_phys(stage_bytes) + 4;
+    const int64_t groups = (width + kCiF - 1) / kCiF;
+    const dim3 grid((unsigned)(rows * groups));
+    if (acc_bits == 32)
+        return launch_recorded(FIR_CINTERP_FAST, NP, fir1d_cplx_interp_kernel<NP, true>, grid, lds, s, (const uint32_t*)x,
+                               (int32_t*)y, width, (uint32_t)groups, U, T, S, PL, t, 0, frac);
+    return launch_recorded(FIR_CINTERP_FAST, NP, fir1d_cplx_interp_kernel<NP, false>, grid, lds, s, (const uint32_t*)x,
+                           (int32_t*)y, width, (uint32_t)groups, U, T, S, PL, t, 32 - acc_bits, frac);
+}
+
+static hipError_t launch_fast(int bucket, const void* x, void* y, int64_t rows, int64_t width, const int32_t* hq, int L,
+                              int U, int frac, int acc_bits, hipStream_t s) {
+    int S = 0;
+    (void)window_of(L, U, &S);
+    const auto go = [&](auto np) {
+        return launch_fast_np<decltype(np)::value>(x, y, rows, width, hq, L, U, S, frac, acc_bits, s);
+    };
+    switch (bucket) {
+        case 1: return go(IntTag<1>{});
+        case 2: return go(IntTag<2>{});
+        case 3: return go(IntTag<3>{});
+        case 4: return go(IntTag<4>{});
+        case 6: return go(IntTag<6>{});
+        case 8: return go(IntTag<8>{});
+        case 10: return go(IntTag<10>{});
+        case 12: return go(IntTag<12>{});
+        case 16: return go(IntTag<16>{});
+        case 20: return go(IntTag<20>{});
+        case 24: return go(IntTag<24>{});
+        case 28: return go(IntTag<28>{});
+        default: return go(IntTag<kCiMaxNP>{});
+    }
+}
+
+template <int STAGE>
+static hipError_t launch_generic(int route, const void* x, void* y, int64_t rows, int64_t width, const int32_t* hq, int L,
+                                 int U, int frac, int acc_bits, hipStream_t s) {
+    using OutT = typename OutTraits<STAGE>::T;
+    const int64_t n_out = rows * width * U;
+    const int64_t blocks = (n_out + kBlock - 1) / kBlock;
+    if (blocks >= ((int64_t)1 << 31)) return hipErrorInvalidValue;
+    const dim3 grid((unsigned)blocks);
+    hipError_t e = hipSuccess;
+    std::lock_guard<std::mutex> hold(g_tab_mu);  // until the launch is enqueued
+    if (route == FIR_CINTERP_GENERIC32) {
+        std::vector<uint32_t> pk(2 * (size_t)L);
+        for (int k = 0; k < L; ++k) {
+            const uint32_t r16 = (uint32_t)hq[2 * k] & 0xFFFFu, i16 = (uint32_t)hq[2 * k + 1] & 0xFFFFu;
+            pk[2 * (size_t)k] = r16 | (((uint32_t)(-hq[2 * k + 1]) & 0xFFFFu) << 16);
+            pk[2 * (size_t)k + 1] = i16 | (r16 << 16);
+        }
+        const uint32_t* pd = (const uint32_t*)table_locked(pk.data(), sizeof(uint32_t) * pk.size(), s, &e);
+        if (!pd) return e;
+        return launch_recorded(route, 0, fir1d_cplx_interp_generic32_kernel<STAGE>, grid, 0, s, (const uint32_t*)x,
+                               (OutT*)y, n_out, width, (int64_t)U, pd, L, 32 - acc_bits, frac);
+    }
+    const int32_t* td = (const int32_t*)table_locked(hq, sizeof(int32_t) * 2 * (size_t)L, s, &e);
+    if (!td) return e;
+    if (route == FIR_CINTERP_GENERIC128)
+        return launch_recorded(route, 0, fir1d_cplx_interp_generic_kernel<STAGE, true>, grid, 0, s, (const int16_t*)x,
+                               (OutT*)y, n_out, width, (int64_t)U, td, L, frac, acc_bits);
+    return launch_recorded(route, 0, fir1d_cplx_interp_generic_kernel<STAGE, false>, grid, 0, s, (const int16_t*)x,
+                           (OutT*)y, n_out, width, (int64_t)U, td, L, frac, acc_bits);
+}
+
+int launch(const int16_t* x, int64_t rows, int64_t width, const int32_t* hq, int L, int up, int frac, int acc_bits,
+           int stage, void* y, hipStream_t stream, std::string* err) {
+    const int rc = check(x, y, rows, width, hq, L, up, frac, acc_bits, stage, err);
+    if (rc) return rc;
+    t_route = FIR_CINTERP_NONE;
+    t_bucket = 0;
+    if (rows == 0 || width == 0) return FIR_OK;
+    int bucket = 0;
+    const int route = route_of((uintptr_t)x, (uintptr_t)y, rows, width, hq, L, up, frac, acc_bits, stage, &bucket);
+    hipError_t e;
+    if (route == FIR_CINTERP_FAST)
+        e = launch_fast(bucket, x, y, rows, width, hq, L, up, frac, acc_bits, stream);
+    else
+        e = fir::with_stage(stage, [&](auto st) {
+            return launch_generic<st>(route, x, y, rows, width, hq, L, up, frac, acc_bits, stream);
+        });
+    if (e != hipSuccess) return *err = std::string("fir1d cplx interp launch failed: ") + hipGetErrorString(e), FIR_EHIP;
+    return FIR_OK;
+}
+
+}  // namespace cinterp
