@@ -1,0 +1,438 @@
+"""The rational resampling complex-tap FIR's C ABI (include/fir_cresample.h, libfir_cresample.so) and
+host layer, without a GPU: the exported symbols, the source id, out_width, the order and texts of the
+refusals of both entries (the restated check_fir1d texts held against libfir_hip.so's own, the rate
+texts against fir_resample_rows'), the dispatch against tests/cresample_cases.predicted_route, and the
+Python layer's own refusals (each before any library call)."""
+from __future__ import annotations
+
+import ctypes
+import inspect
+import os
+import re
+import shutil
+import subprocess
+import sys
+from pathlib import Path
+
+import numpy as np
+import pytest
+
+import cresample_cases as cc
+import fir_hip
+from fir_hip import cdecim, cinterp, cresample
+
+EINVAL, ENODEV = 1, 3
+_NO_DEV = 1 << 20  # a device index no machine has: the device lookup itself refuses it
+ROOT = Path(__file__).resolve().parents[1]
+HEADER = ROOT / "include" / "fir_cresample.h"
+ENTRIES = ("fir_cplx_resample_rows_dev", "fir_cplx_resample_rows")
+
+
+def _declared() -> set[str]:
+    text = re.sub(r"/\*.*?\*/", "", HEADER.read_text(), flags=re.S)
+    return set(re.findall(r"^\s*(?!typedef\b)(?:const\s+)?\w+\s*\*?\s*(\w+)\s*\(", text, flags=re.M))
+
+
+@pytest.fixture(scope="module")
+def lib():
+    if not cresample.lib_path().exists():
+        pytest.fail(f"{cresample.lib_path()} not built; run `python -c 'import __graft_entry__ as g; g.build()'`")
+    return cresample.lib()
+
+
+def test_library_exports_exactly_what_the_header_declares(lib):
+    assert _declared() == set(cresample.EXPORTS) and len(cresample.EXPORTS) == 7
+    raw = ctypes.CDLL(str(cresample.lib_path()))
+    for name in _declared():
+        assert hasattr(raw, name), name
+    # nothing else of the fir_ name space leaves the library, and nothing of the other three libraries'
+    out = subprocess.run(["nm", "-D", "--defined-only", str(cresample.lib_path())], capture_output=True, text=True, check=True)
+    exported = {line.split()[-1] for line in out.stdout.splitlines() if line.split()[-1].startswith("fir")}
+    assert exported == set(cresample.EXPORTS)
+    assert lib.fir_cresample_build_id().decode() == cresample.build_id()
+    assert "fir1d_fixed_rows_cplx_resample" in fir_hip.__all__
+    assert not set(cresample.EXPORTS) & (set(fir_hip.EXPORTS) | set(cdecim.EXPORTS) | set(cinterp.EXPORTS))
+    assert (cresample.ROUTE_NONE, cresample.ROUTE_FAST, cresample.ROUTE_GENERIC32, cresample.ROUTE_GENERIC64,
+            cresample.ROUTE_GENERIC128) == (cc.NONE, cc.FAST, cc.GENERIC32, cc.GENERIC64, cc.GENERIC128) == (0, 1, 2, 3, 4)
+    enum = re.search(r"enum \{([^}]*)\}", HEADER.read_text()).group(1)
+    assert re.findall(r"FIR_CRESAMPLE_(\w+) = (\d)", enum) == [("NONE", "0"), ("FAST", "1"), ("GENERIC32", "2"),
+                                                                ("GENERIC64", "3"), ("GENERIC128", "4")]
+
+
+def test_importing_fir_hip_does_not_load_the_extension_library():
+    probe = ("import sys; import fir_hip; "
+             "maps = open('/proc/self/maps').read(); "
+             "assert 'fir_hip.cresample' not in sys.modules and 'libfir_cresample' not in maps, 'loaded on import'; "
+             "fir_hip.lib(); assert 'libfir_cresample' not in open('/proc/self/maps').read(); "
+             "from fir_hip import cresample; assert 'libfir_cresample' not in open('/proc/self/maps').read(); "
+             "cresample.lib(); maps = open('/proc/self/maps').read(); assert 'libfir_cresample' in maps; "
+             "assert 'libfir_cdecim' not in maps and 'libfir_cinterp' not in maps; print('ok')")
+    env = dict(os.environ, PYTHONPATH=os.pathsep.join([str(Path(fir_hip.__file__).resolve().parents[1])] +
+                                                      ([os.environ["PYTHONPATH"]] if os.environ.get("PYTHONPATH") else [])))
+    r = subprocess.run([sys.executable, "-c", probe], env=env, capture_output=True, text=True)
+    assert r.returncode == 0 and r.stdout.strip() == "ok", r.stderr
+
+
+def test_the_extension_library_needs_none_of_the_others():
+    out = subprocess.run(["readelf", "-d", str(cresample.lib_path())], capture_output=True, text=True, check=True).stdout
+    assert "NEEDED" in out and "libfir_hip" not in out and "libfir_cdecim" not in out and "libfir_cinterp" not in out
+
+
+def test_build_id_is_the_source_id_and_a_stale_library_is_refused(tmp_path):
+    """The library carries the id of the sources it was built from; the loader refuses it when the
+    sources beside it differ -- one flipped byte in each kind of source in turn, no rebuild."""
+    from fir_hip import _srcid_cresample
+
+    assert cresample.build_id() == _srcid_cresample.source_id() and len(cresample.build_id()) == 32
+    pkg = Path(fir_hip.__file__).resolve().parents[1]  # warmup-fir-filter_amd/
+    dst = tmp_path / "tree" / pkg.name
+    shutil.copytree(pkg / "fir_hip", dst / "fir_hip", ignore=shutil.ignore_patterns("__pycache__"))
+    shutil.copytree(pkg / "csrc_cresample", dst / "csrc_cresample", ignore=shutil.ignore_patterns("build"))
+    (dst / "csrc").mkdir()
+    for name in ("fir_common.h", "fir_dispatch.h"):
+        shutil.copy(pkg / "csrc" / name, dst / "csrc" / name)
+    (dst.parent / "include").mkdir()
+    for name in ("fir_cresample.h", "fir_hip.h"):
+        shutil.copy(ROOT / "include" / name, dst.parent / "include" / name)
+    assert _srcid_cresample.source_id(dst) == cresample.build_id()
+    env = {k: v for k, v in os.environ.items() if k != "FIR_HIP_LIB"}
+    probe = (f"import sys; sys.path.insert(0, {str(dst)!r}); from fir_hip import cresample; cresample.lib(); "
+             "print(cresample.build_id())")
+
+    ok = subprocess.run([sys.executable, "-c", probe], env=env, capture_output=True, text=True)
+    assert ok.returncode == 0, ok.stderr
+    assert ok.stdout.strip() == cresample.build_id()
+
+    for src in (dst / "csrc_cresample" / "fir1d_cplx_resample.hip", dst / "csrc_cresample" / "cresample.h",
+                dst / "csrc_cresample" / "capi_cresample.hip", dst / "csrc_cresample" / "Makefile",
+                dst.parent / "include" / "fir_cresample.h", dst / "csrc" / "fir_common.h", dst / "csrc" / "fir_dispatch.h"):
+        data = bytearray(src.read_bytes())
+        i = next(k for k, c in enumerate(data) if chr(c).isalpha())
+        data[i] ^= 0x20  # the case of the first letter, inside the leading comment
+        src.write_bytes(bytes(data))
+        assert _srcid_cresample.source_id(dst) != cresample.build_id(), src
+        bad = subprocess.run([sys.executable, "-c", probe], env=env, capture_output=True, text=True)
+        assert bad.returncode != 0, src
+        assert "built from other sources" in bad.stderr, (src, bad.stderr)
+        data[i] ^= 0x20
+        src.write_bytes(bytes(data))
+    again = subprocess.run([sys.executable, "-c", probe], env=env, capture_output=True, text=True)
+    assert again.returncode == 0, again.stderr
+
+
+def test_out_width(lib):
+    f = lib.fir_cplx_resample_out_width
+    for U in range(1, 18):
+        for D in range(1, 18):
+            for phase in range(D):
+                for width in range(0, 24):
+                    mid = width * U
+                    want = (mid - phase + D - 1) // D if mid > phase else 0
+                    assert f(width, U, D, phase) == want == cresample.out_width(width, U, D, phase) == cc.out_width(width, U, D, phase)
+    for args in ((10, 0, 1, 0), (10, -1, 1, 0), (10, 1, 0, 0), (10, 1, -2, 0), (10, 2, 3, 3), (10, 2, 3, -1), (-1, 1, 1, 0),
+                 (-(1 << 63), 3, 1, 0), (0, 0, 0, 0), (1 << 62, 2, 1, 0), ((1 << 63) - 1, 2, 7, 0), (1 << 40, 1 << 23, 1, 0)):
+        assert f(*args) == -1, args
+    top = (1 << 63) - 1
+    assert f(top, 1, 1, 0) == top and f((1 << 62) - 1, 2, 1, 0) == top - 1 and f(top, 1, 2, 1) == top // 2
+    assert f(top, 1, (1 << 31) - 1, 0) == -(-top // ((1 << 31) - 1)) and f(5, 3, 16, 15) == 0 and f(6, 3, 16, 15) == 1
+    for bad in ((10, 0, 1), (10, 1, 0), (10, -3, 2), (-1, 2, 2), (1 << 62, 2, 3), (10, 2, 3, 3), (10, 2, 3, -1)):
+        with pytest.raises(fir_hip.FirHipError):
+            cresample.out_width(*bad)
+
+
+def _table():
+    """(entry, arguments, status, piece of fir_cresample_last_error) -- None: the device lookup's text.
+    A call that is wrong in two ways names the check that comes first: fir_cplx_rows_dev's own order
+    (the stage, rows and width, hq, taps, frac_bits and acc_bits), then up, decim and phase, then the
+    sizes, then NULL x or y (only for a problem that is not empty), then, for the host form, the device
+    lookup."""
+    h = (ctypes.c_int32 * 6)(1, 2, 3, 4, 5, 6)
+    buf = np.zeros(1024, np.uint8)
+    X = Y = buf.ctypes.data
+    sizes = b"width * up, rows * out_width * 2 * 4 bytes and rows * width * 4 bytes must fit in int64"
+    t = []
+    for fn, tail in (("fir_cplx_resample_rows_dev", None), ("fir_cplx_resample_rows", _NO_DEV)):
+        def add(rc, msg, x=None, rows=0, width=16, hq=h, taps=3, up=3, decim=2, phase=0, frac=12, acc=32, stage=1, y=None,
+                fn=fn, tail=tail):
+            t.append((fn, (x, rows, width, hq, taps, up, decim, phase, frac, acc, stage, y, tail), rc, msg))
+        # empty problems: FIR_OK without a device, NULL pointers and all
+        add(0, b"")
+        add(0, b"", rows=5, width=0)
+        add(0, b"", rows=0, width=1 << 40, stage=0)
+        add(0, b"", rows=1 << 40, width=0, acc=64, frac=40)
+        add(0, b"", rows=0, width=16, up=1 << 30, decim=(1 << 31) - 1, phase=(1 << 31) - 2)
+        add(0, b"", rows=1 << 62, width=0, up=(1 << 31) - 1, x=X)
+        add(0, b"", rows=7, width=1, up=2, decim=16, phase=5)       # mid_width = 2 <= phase
+        add(0, b"", rows=7, width=5, up=3, decim=16, phase=15, x=X)  # mid_width = 15 <= phase
+        # fir_cplx_rows_dev's checks, in its order, with its texts
+        add(EINVAL, b"out_stage must be FIR_OUT_U8_SAT or FIR_OUT_I32", stage=5, rows=-1, hq=None)
+        add(EINVAL, b"out_stage must be FIR_OUT_U8_SAT or FIR_OUT_I32", stage=-1, taps=0, up=0, decim=0)
+        add(EINVAL, b"rows and width must be >= 0", rows=-1, hq=None, taps=0)
+        add(EINVAL, b"rows and width must be >= 0", width=-1, frac=0, up=-1)
+        add(EINVAL, b"hq must not be NULL", hq=None, taps=0, frac=0)
+        add(EINVAL, b"taps must be in [1, 1073741824]", taps=0, frac=0)
+        add(EINVAL, b"taps must be in [1, 1073741824]", taps=-3, rows=1 << 40, width=1 << 40, up=0)
+        add(EINVAL, b"frac_bits and acc_bits must be >= 1", frac=0, rows=1 << 40, width=1 << 40, up=-1)
+        add(EINVAL, b"frac_bits and acc_bits must be >= 1", acc=0, rows=1, decim=0)
+        # then up, decim, phase
+        add(EINVAL, b"up must be >= 1", up=0, decim=0, phase=-1)
+        add(EINVAL, b"up must be >= 1", up=-2, rows=1 << 40, width=1 << 40)
+        add(EINVAL, b"decim must be >= 1", decim=0, phase=-1, rows=1)
+        add(EINVAL, b"decim must be >= 1", decim=-5, rows=1 << 40, width=1 << 40)
+        add(EINVAL, b"phase must be in [0, decim)", phase=2, rows=1 << 40, width=1 << 40)
+        add(EINVAL, b"phase must be in [0, decim)", phase=-1, rows=1)
+        # then the sizes, with a text of their own
+        add(EINVAL, sizes, rows=1 << 40, width=1 << 40)
+        add(EINVAL, sizes, rows=1, width=1 << 62)                                  # width * up
+        add(EINVAL, sizes, rows=1, width=1 << 60, up=1, decim=1, x=X, y=Y)         # rows * out_width * 8: 2^63
+        add(EINVAL, sizes, rows=1 << 30, width=1 << 29, up=4, decim=1)             # rows * width fits, * up * 8 does not
+        add(EINVAL, sizes, rows=1 << 31, width=1 << 30, up=1, decim=1 << 30, x=X, y=Y)  # rows * width * 4 alone
+        # then the pointers, only when something would be computed
+        add(EINVAL, b"x and y must not be NULL", rows=1)
+        add(EINVAL, b"x and y must not be NULL", rows=1, x=X)
+        add(EINVAL, b"x and y must not be NULL", rows=1, y=Y, stage=0)
+        add(EINVAL, b"x and y must not be NULL", rows=1 << 29, width=1 << 29, up=2, decim=1)  # the largest legal size
+        if tail is not None:  # the host form gets as far as the device lookup
+            add(ENODEV, None, rows=1, x=X, y=Y)
+            add(ENODEV, None, rows=2, x=X, y=Y, stage=0, acc=64, up=1, decim=1)
+    return t, buf
+
+
+def test_refusal_order_of_both_entries(lib):
+    n = ctypes.c_int(0)
+    first = fir_hip.lib()
+    have = first.fir_device_count(ctypes.byref(n)) == 0 and n.value > 0
+    nodev = b"out of range" if have else b"no HIP device available"
+    table, keep = _table()
+    assert {fn for fn, *_ in table} == set(ENTRIES)
+    bad = []
+    for fn, args, want, msg in table:
+        rc = getattr(lib, fn)(*args)
+        err = lib.fir_cresample_last_error()
+        if rc != want or (want and (nodev if msg is None else msg) not in err):
+            bad.append((fn, args, want, msg, rc, err))
+        # the route query refuses what the entries refuse, and calls an empty problem NONE
+        x, rows, width, hq, taps, up, decim, phase, frac, acc, stage, y, _ = args
+        r = lib.fir_cplx_resample_route(x or 0, y or 0, rows, width, hq, taps, up, decim, phase, frac, acc, stage, None)
+        if want == EINVAL and (r != -1 or msg not in lib.fir_cresample_last_error()):
+            bad.append(("route", args, -1, msg, r, lib.fir_cresample_last_error()))
+        if want == 0 and r != cc.NONE:
+            bad.append(("route", args, cc.NONE, b"", r, b""))
+    assert not bad, "\n".join(f"{fn}{args}: want {want} {msg!r}, got {rc} {err!r}" for fn, args, want, msg, rc, err in bad)
+    del keep
+
+
+def test_refusal_texts_are_the_first_librarys(lib):
+    """Every refusal fir_cplx_rows also makes has, character for character, fir_cplx_rows' text, and
+    the refusals of up, decim and phase fir_resample_rows': the check on the restated checks."""
+    first = fir_hip.lib()
+    h = (ctypes.c_int32 * 6)(1, 2, 3, 4, 5, 6)
+    base = dict(x=None, rows=1, width=16, hq=h, taps=3, frac=12, acc=32, stage=1, y=None)
+    cases = [dict(stage=5), dict(stage=-1), dict(rows=-1), dict(width=-1), dict(rows=-5, width=-5), dict(hq=None),
+             dict(taps=0), dict(taps=-1), dict(taps=(1 << 30) + 1), dict(frac=0), dict(acc=0), dict(frac=-3, acc=-3),
+             dict(), dict(stage=7, rows=-1, hq=None, taps=0, frac=0)]
+    for over in cases:
+        a = dict(base, **over)
+        for fn1, fn2, tail in (("fir_cplx_rows_dev", "fir_cplx_resample_rows_dev", None), ("fir_cplx_rows", "fir_cplx_resample_rows", _NO_DEV)):
+            rc1 = getattr(first, fn1)(a["x"], a["rows"], a["width"], a["hq"], a["taps"], a["frac"], a["acc"], a["stage"], a["y"], tail)
+            text1 = bytes(first.fir_last_error())
+            rc2 = getattr(lib, fn2)(a["x"], a["rows"], a["width"], a["hq"], a["taps"], 3, 2, 1, a["frac"], a["acc"], a["stage"], a["y"], tail)
+            text2 = bytes(lib.fir_cresample_last_error())
+            assert rc1 == rc2 == EINVAL and text1 == text2 and text1, (over, fn2, rc1, rc2, text1, text2)
+    hr = (ctypes.c_int32 * 3)(1, 2, 3)
+    for up, decim, phase, text in ((0, 2, 0, b"up must be >= 1"), (-1, 0, 5, b"up must be >= 1"), (2, 0, 0, b"decim must be >= 1"),
+                                   (2, -3, -1, b"decim must be >= 1"), (2, 3, 3, b"phase must be in [0, decim)"),
+                                   (2, 3, -1, b"phase must be in [0, decim)")):
+        rc1 = first.fir_resample_rows_dev(None, fir_hip.IN_I16, 1, 16, 2, hr, 3, up, decim, phase, 12, 32, 1, None, None)
+        text1 = bytes(first.fir_last_error())
+        rc2 = lib.fir_cplx_resample_rows_dev(None, 1, 16, h, 3, up, decim, phase, 12, 32, 1, None, None)
+        assert rc1 == rc2 == EINVAL and text1 == bytes(lib.fir_cresample_last_error()) == text, (up, decim, phase, text1)
+
+
+def test_empty_problems_need_no_device_and_launch_nothing(lib):
+    h = (ctypes.c_int32 * 10)(-256, 3, -1024, 0, 6656, -7, -1024, 0, -256, 1)
+    r, b = ctypes.c_int(-1), ctypes.c_int(-1)
+    for stage in (0, 1):
+        for rows, width, U, D, phase in ((0, 0, 1, 1, 0), (0, 4096, 3, 2, 1), (7, 0, 3, 2, 0), (0, 1, 16, 16, 15), (5, 0, 17, 3, 2),
+                                         (0, 0, 1 << 30, 1 << 30, 5), (3, 1, 2, 16, 2), (3, 1, 2, 16, 15), (1, 5, 3, 17, 16)):
+            for acc, frac in ((32, 12), (64, 40), (8, 1)):
+                rc = lib.fir_cplx_resample_rows_dev(None, rows, width, h, 5, U, D, phase, frac, acc, stage, None, None)
+                assert rc == 0, (stage, rows, width, lib.fir_cresample_last_error())
+                rc = lib.fir_cplx_resample_rows(None, rows, width, h, 5, U, D, phase, frac, acc, stage, None, _NO_DEV)
+                assert rc == 0, (stage, rows, width, lib.fir_cresample_last_error())
+                assert lib.fir_cplx_resample_last_launch(ctypes.byref(r), ctypes.byref(b)) == 0 and (r.value, b.value) == (0, 0)
+                assert lib.fir_cplx_resample_route(0, 0, rows, width, h, 5, U, D, phase, frac, acc, stage, ctypes.byref(b)) == cc.NONE
+    assert lib.fir_cplx_resample_last_launch(None, None) == 0
+    assert cresample.last_launch() == (cc.NONE, 0)
+
+
+def _route(lib, x, y, rows, width, hq, U, D, phase=0, frac=12, acc=32, stage=1):
+    h = np.ascontiguousarray(np.asarray(hq, dtype=np.int64).reshape(-1, 2), dtype=np.int32)
+    b = ctypes.c_int(-1)
+    r = lib.fir_cplx_resample_route(x, y, rows, width, h.ctypes.data_as(ctypes.c_void_p), h.shape[0], U, D, phase, frac, acc,
+                                    stage, ctypes.byref(b))
+    return r, b.value
+
+
+def test_route_is_the_documented_dispatch(lib):
+    """fir_cplx_resample_route against predicted_route, every dispatch reason taken one at a time: U and
+    D at 15, 16, 17 (and 1, 2), every tap count 1..130 (so 128 / 129 taps, 32 / 33 per phase and every
+    tap bucket), x off 16 by 0, 2, 4 and 8 bytes, y off by 0 and 4, rows of 4k, 4k + 1 and 4k + 2 frames
+    against one row, tap values at the ends of int16 and past them, the bit widths at their thresholds,
+    both stages, the grid limits."""
+    X = Y = 1 << 30
+    rng = np.random.default_rng(5)
+    n = 0
+
+    def hold(*a, **k):
+        nonlocal n
+        n += 1
+        got, want = _route(lib, *a, **k), cc.predicted_route(*a, **k)
+        assert got == want, (a[:4], len(a[4]), a[5:], k, got, want)
+        return got
+
+    seen, buckets = set(), set()
+    rates = [(1, 1), (1, 2), (2, 1), (2, 3), (3, 2), (4, 6), (15, 16), (16, 15), (16, 16), (16, 17), (17, 16), (15, 2), (2, 15)]
+    for L in range(1, 131):
+        hq = cc.taps(rng, L)
+        for U, D in rates:
+            phase = L % D
+            fast_rate = 2 <= U <= 16 and 2 <= D <= 16
+            fast_taps = L <= min(128, 32 * U)
+            for xo in (0, 4, 8):
+                for yo in (0, 4):
+                    for rows, width in ((1, 1001), (3, 1000), (3, 1001), (3, 1002)):
+                        r, b = hold(X + xo, Y + yo, rows, width, hq, U, D, phase)
+                        seen.add(r)
+                        if r == cc.FAST:
+                            assert fast_rate and fast_taps and xo == 0 and (rows == 1 or width % 4 == 0)
+                            assert b == cc.bucket(L, U, D, phase) and b in cc.BUCKETS
+                            buckets.add(b)
+                        else:
+                            assert b == 0 and (not fast_rate or not fast_taps or xo or (rows > 1 and width % 4))
+    assert seen == {cc.FAST, cc.GENERIC32} and buckets == set(cc.BUCKETS)
+    base = cc.taps(rng, 9)
+    wide = np.full((2**16 + 9, 2), 2**31 - 1)
+    wide[::2] *= -1
+    for U, D, phase in ((1, 1, 0), (3, 2, 1), (16, 16, 15), (17, 2, 0), (2, 17, 16)):
+        fast_rate = 2 <= U <= 16 and 2 <= D <= 16
+        for stage in (cc.OUT_I32, cc.OUT_U8_SAT):
+            for poke, at in ((32767, 0), (-32767, 1), (32768, 0), (32768, 1), (-32768, 0), (-32768, 1), (1 << 20, 0), (-(1 << 20), 1)):
+                hq = base.copy()
+                hq[4, at] = poke
+                r, _ = hold(X, Y, 1, 4096, hq, U, D, phase, 12, 32, stage)
+                assert (r in (cc.FAST, cc.GENERIC32)) == (abs(poke) == 32767)
+            for acc, frac in ((32, 12), (33, 12), (64, 12), (32, 31), (32, 32), (31, 31), (1, 1), (63, 40), (64, 64), (128, 3)):
+                r, _ = hold(X, Y, 1, 4096, base, U, D, phase, frac, acc, stage)
+                assert (r == cc.GENERIC64) == (acc > 32 or frac > 31)
+                assert (r == cc.FAST) == (acc <= 32 and frac <= 31 and fast_rate and stage == cc.OUT_I32)
+                for xo in (2, 6):  # an x that is only int16 aligned
+                    assert hold(X + xo, Y, 1, 4096, base, U, D, phase, frac, acc, stage)[0] == cc.GENERIC64
+                r, _ = hold(X, Y, 2, 150, wide, U, D, phase, frac, acc, stage)
+                assert r == (cc.GENERIC128 if acc >= 64 else cc.GENERIC64)
+                assert hold(X, Y, 2, 150, wide[:2**16 - 1], U, D, phase, frac, acc, stage)[0] == cc.GENERIC64
+    # the grid: a row of 2^40 frames, and rows x workgroups at 2^31 (U = D = 2: 1024 output frames per workgroup)
+    tiny = [[1, 1]]
+    assert hold(X, Y, 1, (1 << 40) - 4, tiny, 16, 16)[0] == cc.FAST and hold(X, Y, 1, 1 << 40, tiny, 16, 16)[0] == cc.GENERIC32
+    assert hold(X, Y, (1 << 20) - 1, 1 << 20, tiny, 2, 2)[0] == cc.FAST      # (2^20 - 1) rows x 2^10 workgroups < 2^30
+    assert hold(X, Y, 1 << 22, 1 << 20, tiny, 2, 2)[0] == cc.GENERIC32       # 2^22 rows x 2^10 workgroups = 2^32
+    assert hold(X, Y, 1 << 21, 1 << 20, tiny, 2, 2)[0] == cc.GENERIC32       # = 2^31
+    assert hold(X, Y, (1 << 21) - 1, 1 << 20, tiny, 2, 2)[0] == cc.FAST      # < 2^31
+    assert n > 10000
+    # the Python wrapper: a Route, and FirHipError for a refused call
+    assert cresample.route(X, Y, 1, 100, base, 4, 3) == (cc.FAST, 3) == tuple(cresample.Route(cc.FAST, 3))  # 9 taps at U = 4
+    for bad, text in (((0, 2), "up must be >= 1"), ((2, 0), "decim must be >= 1"), ((2, 3, 3), "phase must be in")):
+        with pytest.raises(fir_hip.FirHipError, match=text):
+            cresample.route(X, Y, 1, 100, base, *bad)
+
+
+class _NoLibrary:
+    """Stands in for the loaded library: any call through it fails the test."""
+
+    def __getattr__(self, name):
+        raise AssertionError(f"the library was called ({name}) for a call the host layer must refuse")
+
+
+def test_python_layer_refuses_before_any_library_call(monkeypatch):
+    monkeypatch.setattr(cresample, "lib", lambda: _NoLibrary())
+    x = np.zeros((4, 16), np.int16)
+    h = [[1, 2], [3, 4], [5, 6]]
+    for f in (cresample.fir1d_fixed_rows_cplx_resample, fir_hip.fir1d_fixed_rows_cplx_resample):
+        for bad in (x.astype(np.uint8), x.astype(np.int32), x.astype(np.float32), x.astype(np.complex64), x.tolist()):
+            with pytest.raises(fir_hip.FirHipError, match="x must be an int16 array"):
+                f(bad, h, 3, 2)
+        with pytest.raises(fir_hip.FirHipError, match="at least one axis"):
+            f(np.zeros((), np.int16), h, 3, 2)
+        for odd in (np.zeros((4, 15), np.int16), np.zeros(1, np.int16), np.zeros((2, 3, 7), np.int16)):
+            with pytest.raises(fir_hip.FirHipError, match="even number of values"):
+                f(odd, h, 3, 2)
+        for taps in ([1, 2, 3], [[1, 2, 3]] * 4, np.zeros((5, 3), np.int64), np.zeros((0, 2), np.int64), [], 7):
+            with pytest.raises(fir_hip.FirHipError, match=r"non-empty \(taps, 2\) array"):
+                f(x, taps, 3, 2)
+        with pytest.raises(fir_hip.FirHipError, match="hq must be an integer array"):
+            f(x, [[1.0, 2.0]], 3, 2)
+        with pytest.raises(fir_hip.FirHipError, match="must fit in int32"):
+            f(x, [[1, 2**31]], 3, 2)
+        for U in (0, -1):
+            with pytest.raises(fir_hip.FirHipError, match="up must be >= 1"):
+                f(x, h, U, 2)
+        for D in (0, -1):
+            with pytest.raises(fir_hip.FirHipError, match="decim must be >= 1"):
+                f(x, h, 3, D)
+        for phase in (2, -1):
+            with pytest.raises(fir_hip.FirHipError, match="phase must be in"):
+                f(x, h, 3, 2, phase)
+        # out=: x's leading axes x 2 * out_width, int32 (uint8 for the u8 stage): 8 frames at 3 / 2 are 12 frames
+        ro = np.zeros((4, 24), np.int32)
+        ro.flags.writeable = False
+        for out in (np.zeros((4, 24), np.uint8), np.zeros((4, 16), np.int32), np.zeros((4, 26), np.int32), np.zeros((4, 22), np.int32),
+                    np.zeros((24, 4), np.int32).T, [[0] * 24] * 4, ro):
+            with pytest.raises(fir_hip.FirHipError, match="out must"):
+                f(x, h, 3, 2, out=out)
+        with pytest.raises(fir_hip.FirHipError, match="out must be uint8"):
+            f(x, h, 3, 2, out_stage=fir_hip.OUT_U8_SAT, out=np.zeros((4, 24), np.int32))
+        big = np.zeros(256, np.int16)
+        with pytest.raises(fir_hip.FirHipError, match="overlap"):
+            f(big[:32], h, 2, 1, out=big.view(np.int32)[8:72])
+
+
+def test_python_layer_passes_the_call_on(monkeypatch):
+    """An accepted call reaches fir_cplx_resample_rows once, with rows, width in FRAMES, the taps and the
+    scalars, and an output of the resampled shape."""
+    calls = []
+
+    class Rec:
+        def fir_cplx_resample_rows(self, *a):
+            taps = tuple((ctypes.c_int32 * (2 * a[4])).from_address(a[3].value))
+            calls.append((a[1], a[2], taps) + tuple(a[4:11]) + (a[12],))
+            return 0
+
+    monkeypatch.setattr(cresample, "lib", lambda: Rec())
+    x = np.zeros((3, 5, 16), np.int16)
+    y = fir_hip.fir1d_fixed_rows_cplx_resample(x, [[2**31 - 1, -2**31], [3, -4]], 3, 2, 1, 7, 24, device=2)
+    assert y.shape == (3, 5, 24) and y.dtype == np.int32  # 8 frames: 24 stuffed, 12 kept from frame 1
+    assert calls == [(15, 8, (2**31 - 1, -2**31, 3, -4), 2, 3, 2, 1, 7, 24, fir_hip.OUT_I32, 2)]
+    y = cresample.fir1d_fixed_rows_cplx_resample(x[..., :0], np.array([[1, 2]], np.int8), 4, 3, out_stage=fir_hip.OUT_U8_SAT)
+    assert y.shape == (3, 5, 0) and y.dtype == np.uint8 and calls[-1][:2] == (0, 0)
+    y = cresample.fir1d_fixed_rows_cplx_resample(x[..., :2], [[1, 2]], 2, 16, 5)  # mid_width 2 <= phase
+    assert y.shape == (3, 5, 0) and calls[-1][:2] == (15, 1)
+    out = np.empty((3, 5, 16), np.int32)
+    assert cresample.fir1d_fixed_rows_cplx_resample(x, [[1, 2]], 1, 1, out=out) is out
+    for f in (cresample.fir1d_fixed_rows_cplx_resample, fir_hip.fir1d_fixed_rows_cplx_resample):
+        sig = inspect.signature(f)
+        assert list(sig.parameters) == ["x", "hq", "up", "decim", "phase", "frac_bits", "acc_bits", "out_stage", "device", "out"]
+        assert {k: v.default for k, v in sig.parameters.items() if v.default is not inspect.Parameter.empty} == dict(
+            phase=0, frac_bits=12, acc_bits=32, out_stage=fir_hip.OUT_I32, device=0, out=None)
+
+
+def test_the_device_entry_follows_torch_cinterp():
+    from fir_hip import torch_cinterp, torch_cresample
+
+    sig = inspect.signature(torch_cresample.fir1d_fixed_rows_cplx_resample_dev)
+    assert list(sig.parameters) == ["x", "hq", "up", "decim", "phase", "frac_bits", "acc_bits", "out_stage", "out", "stream"]
+    ref = inspect.signature(torch_cinterp.fir1d_fixed_rows_cplx_interp_dev)
+    for k in ("frac_bits", "acc_bits", "out_stage", "out", "stream"):
+        assert sig.parameters[k].default == ref.parameters[k].default
+    assert sig.parameters["phase"].default == 0
+    assert torch_cresample.CplxTaps is torch_cinterp.CplxTaps
+    assert set(torch_cresample.__all__) == {"CplxTaps", "fir1d_fixed_rows_cplx_resample_dev"}

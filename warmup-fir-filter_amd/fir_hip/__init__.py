@@ -9,7 +9,8 @@ Host-array entry points (NumPy in, NumPy out, synchronous):
     fir1d_fixed_rows, fir1d_fixed_rows_decim, fir1d_fixed_rows_interp, fir1d_fixed_rows_resample,
     fir1d_fixed_rows_cplx, fir1d_fixed_rows_cplx_decim (the extension library libfir_cdecim.so, loaded on
     first use by :mod:`fir_hip.cdecim`), fir1d_fixed_rows_cplx_interp (libfir_cinterp.so, loaded on first use by
-    :mod:`fir_hip.cinterp`), fir1d_fixed_rows_multi,
+    :mod:`fir_hip.cinterp`), fir1d_fixed_rows_cplx_resample (libfir_cresample.so, loaded on first use by
+    :mod:`fir_hip.cresample`), fir1d_fixed_rows_multi,
     fir1d_fixed_rows_sharded, fir2d_fixed, fir2d_ideal, fir1d_ideal_rows, compare_metrics, restore_u8, and the stage drivers' image batches
     fir1d_fixed_images_multi / fir1d_ideal_images_multi (page-locked staging: host_empty)
 Device entry points (torch tensors on a HIP device, enqueued on the current stream):
@@ -36,7 +37,7 @@ __all__ = [
     "fir1d_ideal_images_multi", "host_empty", "TIMING_KEYS", "decim_out_width", "fir1d_fixed_rows_decim",
     "interp_out_width", "fir1d_fixed_rows_interp", "resample_out_width", "fir1d_fixed_rows_resample",
     "fir1d_fixed_rows_cplx", "fir1d_fixed_rows_cplx_decim", "fir1d_fixed_rows_cplx_interp", "Launch", "launch_log",
-    "kernel_census",
+    "kernel_census", "fir1d_fixed_rows_cplx_resample",
 ]
 
 IN_U8, IN_I16 = 0, 1
@@ -625,6 +626,17 @@ def fir1d_fixed_rows_cplx_interp(x: np.ndarray, hq, up: int, frac_bits: int = 12
     from . import cinterp
 
     return cinterp.fir1d_fixed_rows_cplx_interp(x, hq, up, frac_bits, acc_bits, out_stage, device, out)
+
+
+def fir1d_fixed_rows_cplx_resample(x: np.ndarray, hq, up: int, decim: int, phase: int = 0, frac_bits: int = 12,
+                                   acc_bits: int = 32, out_stage: int = OUT_I32, device: int = 0,
+                                   out: np.ndarray | None = None) -> np.ndarray:
+    """Frames ``phase, phase + decim, ...`` of fir1d_fixed_rows_cplx_interp(x, hq, up), in one polyphase
+    pass: :func:`fir_hip.cresample.fir1d_fixed_rows_cplx_resample`, whose extension library
+    (libfir_cresample.so) is loaded on first use."""
+    from . import cresample
+
+    return cresample.fir1d_fixed_rows_cplx_resample(x, hq, up, decim, phase, frac_bits, acc_bits, out_stage, device, out)
 
 
 def fir1d_fixed_rows_sharded(x: np.ndarray, hq, frac_bits: int = 12, acc_bits: int = 32,
