@@ -77,6 +77,7 @@ def test_stale_library_is_refused(tmp_path):
     dst = tmp_path / "tree" / pkg.name
     shutil.copytree(pkg / "fir_hip", dst / "fir_hip", ignore=shutil.ignore_patterns("__pycache__"))
     shutil.copytree(pkg / "csrc_cdecim", dst / "csrc_cdecim", ignore=shutil.ignore_patterns("build"))
+    shutil.copytree(pkg / "csrc_cext", dst / "csrc_cext")
     (dst / "csrc").mkdir()
     for name in ("fir_common.h", "fir_dispatch.h"):
         shutil.copy(pkg / "csrc" / name, dst / "csrc" / name)
@@ -92,7 +93,8 @@ def test_stale_library_is_refused(tmp_path):
     assert ok.stdout.strip() == cdecim.build_id()
 
     for src in (dst / "csrc_cdecim" / "fir1d_cplx_decim.hip", dst / "csrc_cdecim" / "cdecim.h", dst / "csrc_cdecim" / "Makefile",
-                dst.parent / "include" / "fir_cdecim.h", dst / "csrc" / "fir_common.h", dst / "csrc" / "fir_dispatch.h"):
+                dst.parent / "include" / "fir_cdecim.h", dst / "csrc" / "fir_common.h", dst / "csrc" / "fir_dispatch.h",
+                *sorted((dst / "csrc_cext").iterdir())):
         data = bytearray(src.read_bytes())
         i = next(k for k, c in enumerate(data) if chr(c).isalpha())
         data[i] ^= 0x20  # the case of the first letter, inside the leading comment

@@ -80,6 +80,7 @@ def test_stale_library_is_refused(tmp_path):
     dst = tmp_path / "tree" / pkg.name
     shutil.copytree(pkg / "fir_hip", dst / "fir_hip", ignore=shutil.ignore_patterns("__pycache__"))
     shutil.copytree(pkg / "csrc_cinterp", dst / "csrc_cinterp", ignore=shutil.ignore_patterns("build"))
+    shutil.copytree(pkg / "csrc_cext", dst / "csrc_cext")
     (dst / "csrc").mkdir()
     for name in ("fir_common.h", "fir_dispatch.h"):
         shutil.copy(pkg / "csrc" / name, dst / "csrc" / name)
@@ -96,7 +97,8 @@ def test_stale_library_is_refused(tmp_path):
 
     for src in (dst / "csrc_cinterp" / "fir1d_cplx_interp.hip", dst / "csrc_cinterp" / "cinterp.h",
                 dst / "csrc_cinterp" / "capi_cinterp.hip", dst / "csrc_cinterp" / "Makefile",
-                dst.parent / "include" / "fir_cinterp.h", dst / "csrc" / "fir_common.h", dst / "csrc" / "fir_dispatch.h"):
+                dst.parent / "include" / "fir_cinterp.h", dst / "csrc" / "fir_common.h", dst / "csrc" / "fir_dispatch.h",
+                *sorted((dst / "csrc_cext").iterdir())):
         data = bytearray(src.read_bytes())
         i = next(k for k, c in enumerate(data) if chr(c).isalpha())
         data[i] ^= 0x20  # the case of the first letter, inside the leading comment

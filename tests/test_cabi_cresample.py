@@ -81,20 +81,21 @@ def test_the_extension_library_needs_none_of_the_others():
 def test_build_id_is_the_source_id_and_a_stale_library_is_refused(tmp_path):
     """The library carries the id of the sources it was built from; the loader refuses it when the
     sources beside it differ -- one flipped byte in each kind of source in turn, no rebuild."""
-    from fir_hip import _srcid_cresample
+    from fir_hip import _srcid_ext
 
-    assert cresample.build_id() == _srcid_cresample.source_id() and len(cresample.build_id()) == 32
+    assert cresample.build_id() == _srcid_ext.source_id("cresample") and len(cresample.build_id()) == 32
     pkg = Path(fir_hip.__file__).resolve().parents[1]  # warmup-fir-filter_amd/
     dst = tmp_path / "tree" / pkg.name
     shutil.copytree(pkg / "fir_hip", dst / "fir_hip", ignore=shutil.ignore_patterns("__pycache__"))
     shutil.copytree(pkg / "csrc_cresample", dst / "csrc_cresample", ignore=shutil.ignore_patterns("build"))
+    shutil.copytree(pkg / "csrc_cext", dst / "csrc_cext")
     (dst / "csrc").mkdir()
     for name in ("fir_common.h", "fir_dispatch.h"):
         shutil.copy(pkg / "csrc" / name, dst / "csrc" / name)
     (dst.parent / "include").mkdir()
     for name in ("fir_cresample.h", "fir_hip.h"):
         shutil.copy(ROOT / "include" / name, dst.parent / "include" / name)
-    assert _srcid_cresample.source_id(dst) == cresample.build_id()
+    assert _srcid_ext.source_id("cresample", dst) == cresample.build_id()
     env = {k: v for k, v in os.environ.items() if k != "FIR_HIP_LIB"}
     probe = (f"import sys; sys.path.insert(0, {str(dst)!r}); from fir_hip import cresample; cresample.lib(); "
              "print(cresample.build_id())")
@@ -105,12 +106,13 @@ def test_build_id_is_the_source_id_and_a_stale_library_is_refused(tmp_path):
 
     for src in (dst / "csrc_cresample" / "fir1d_cplx_resample.hip", dst / "csrc_cresample" / "cresample.h",
                 dst / "csrc_cresample" / "capi_cresample.hip", dst / "csrc_cresample" / "Makefile",
-                dst.parent / "include" / "fir_cresample.h", dst / "csrc" / "fir_common.h", dst / "csrc" / "fir_dispatch.h"):
+                dst.parent / "include" / "fir_cresample.h", dst / "csrc" / "fir_common.h", dst / "csrc" / "fir_dispatch.h",
+                *sorted((dst / "csrc_cext").iterdir())):
         data = bytearray(src.read_bytes())
         i = next(k for k, c in enumerate(data) if chr(c).isalpha())
         data[i] ^= 0x20  # the case of the first letter, inside the leading comment
         src.write_bytes(bytes(data))
-        assert _srcid_cresample.source_id(dst) != cresample.build_id(), src
+        assert _srcid_ext.source_id("cresample", dst) != cresample.build_id(), src
         bad = subprocess.run([sys.executable, "-c", probe], env=env, capture_output=True, text=True)
         assert bad.returncode != 0, src
         assert "built from other sources" in bad.stderr, (src, bad.stderr)

@@ -50,18 +50,22 @@
 //    4-byte aligned): 32-bit wrap-around sums, two v_dot2 per tap over a packed (A, B) table, and a
 //    wave-uniform untested loop for workgroups whose windows all lie inside one row.
 //    fir1d_cplx_decim_generic_kernel: exact 64-bit sums, or 128-bit when needs_wide says so.
-#include <cstring>
 #include <mutex>
 #include <string>
 #include <type_traits>
 #include <vector>
 
 #include "cdecim.h"
+#include "cext_launch.h"
 #include "fir_common.h"
 #include "fir_dispatch.h"
 
 namespace cdecim {
 
+using cext::dot2_ok;
+using cext::launch_recorded;
+using cext::needs_wide;
+using cext::table_locked;
 using fir::dot2_acc;
 using fir::IntTag;
 using fir::kBlock;
@@ -287,12 +291,7 @@ int64_t out_width(int64_t width, int decim, int phase) {
 // (tests/test_cabi_cdecim.py holds them against libfir_hip.so's), then the header's checks 2 to 5.
 int check(const void* x, const void* y, int64_t rows, int64_t width, const int32_t* hq, int L, int decim, int phase,
           int frac, int acc_bits, int stage, int64_t* ow, std::string* err) {
-    if (stage != FIR_OUT_U8_SAT && stage != FIR_OUT_I32)
-        return *err = "out_stage must be FIR_OUT_U8_SAT or FIR_OUT_I32", FIR_EINVAL;
-    if (rows < 0 || width < 0) return *err = "rows and width must be >= 0", FIR_EINVAL;
-    if (!hq) return *err = "hq must not be NULL", FIR_EINVAL;
-    if (L < 1 || L > FIR_MAX_TAPS) return *err = "taps must be in [1, " + std::to_string(FIR_MAX_TAPS) + "]", FIR_EINVAL;
-    if (frac < 1 || acc_bits < 1) return *err = "frac_bits and acc_bits must be >= 1", FIR_EINVAL;
+    if (const int rc = cext::check_head(rows, width, hq, L, frac, acc_bits, stage, err)) return rc;
     if (decim < 1) return *err = "decim must be >= 1", FIR_EINVAL;
     if (phase < 0 || phase >= decim) return *err = "phase must be in [0, decim)", FIR_EINVAL;
     int64_t rw = 0;
@@ -301,24 +300,6 @@ int check(const void* x, const void* y, int64_t rows, int64_t width, const int32
     *ow = out_width(width, decim, phase);
     if (rows != 0 && *ow != 0 && (!x || !y)) return *err = "x and y must not be NULL", FIR_EINVAL;
     return FIR_OK;
-}
-
-// 32-bit wrap-around sums over v_dot2_i32_i16 are exact for the call: both tap parts (and -hi) fit
-// in int16, and the wrap and the rounding shift stay inside 32 bits
-static bool dot2_ok(const int32_t* hq, int L, int frac, int acc_bits) {
-    if (acc_bits > 32 || frac > 31) return false;
-    for (int64_t k = 0; k < 2 * (int64_t)L; ++k)
-        if (hq[k] < -32767 || hq[k] > 32767) return false;
-    return true;
-}
-
-// csrc/fir1d.hip's needs_wide for int16 samples over the 2 L tap parts: a no-wrap call whose exact
-// sum could reach 2^63
-static bool needs_wide(const int32_t* hq, int L, int acc_bits) {
-    if (acc_bits < 64) return false;
-    unsigned __int128 habs = 0;
-    for (int64_t k = 0; k < 2 * (int64_t)L; ++k) habs += (unsigned __int128)(hq[k] < 0 ? -(int64_t)hq[k] : (int64_t)hq[k]);
-    return habs * 32768 >= ((unsigned __int128)1 << 63);
 }
 
 static int bucket_of(int L) {
@@ -345,74 +326,8 @@ int route_of(uintptr_t x, uintptr_t y, int64_t rows, int64_t width, int64_t ow, 
     return needs_wide(hq, L, acc_bits) ? FIR_CDECIM_GENERIC128 : FIR_CDECIM_GENERIC64;
 }
 
-// ---- the launch wrapper: every kernel of the library is launched here, and what was launched is
-// kept for last_launch (this thread)
-thread_local int t_route = FIR_CDECIM_NONE, t_bucket = 0;
-
-template <typename... KArgs, typename... Args>
-static hipError_t launch_recorded(int route, int bucket, void (*kernel)(KArgs...), dim3 grid, size_t shmem,
-                                  hipStream_t s, Args... args) {
-    hipLaunchKernelGGL(kernel, grid, dim3(kBlock), shmem, s, (KArgs)args...);
-    const hipError_t e = hipGetLastError();
-    if (e == hipSuccess) {
-        t_route = route;
-        t_bucket = bucket;
-    }
-    return e;
-}
-
-void last_launch(int* route, int* bucket) {
-    if (route) *route = t_route;
-    if (bucket) *bucket = t_bucket;
-}
-
-// ---- the generic kernels' tap tables: device copies cached per device by the exact bytes they
-// hold, confirmed by comparing them, uploaded once (complete before the call returns).  A caller
-// holds g_tab_mu from the lookup until its launch is enqueued, so when the cached bytes of a
-// device pass kTabCap a device-wide synchronise leaves no launch that reads a table outstanding
-// and the device's tables are freed; a table used inside a stream capture is never freed (the
-// graph may replay it), and nothing is evicted while a capture is under way.
-constexpr size_t kTabCap = size_t(64) << 20;
-struct Table {
-    int dev;
-    std::vector<uint8_t> key;
-    void* d;
-    bool pinned;
-};
-static std::mutex g_tab_mu;
-static std::vector<Table> g_tabs;
-
-static const void* table_locked(const void* host, size_t bytes, hipStream_t s, hipError_t* e) {
-    int dev = 0;
-    if ((*e = hipGetDevice(&dev)) != hipSuccess) return nullptr;
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    const bool capturing = hipStreamIsCapturing(s, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone;
-    size_t held = 0;
-    for (Table& t : g_tabs) {
-        if (t.dev != dev) continue;
-        if (t.key.size() == bytes && std::memcmp(t.key.data(), host, bytes) == 0) {
-            t.pinned |= capturing;
-            return t.d;
-        }
-        held += t.key.size();
-    }
-    if (held && held + bytes > kTabCap && !capturing && hipDeviceSynchronize() == hipSuccess) {
-        for (size_t i = g_tabs.size(); i-- > 0;)
-            if (g_tabs[i].dev == dev && !g_tabs[i].pinned) {
-                (void)hipFree(g_tabs[i].d);
-                g_tabs.erase(g_tabs.begin() + (ptrdiff_t)i);
-            }
-    }
-    void* d = nullptr;
-    if ((*e = hipMalloc(&d, bytes)) != hipSuccess) return nullptr;
-    if ((*e = hipMemcpy(d, host, bytes, hipMemcpyHostToDevice)) != hipSuccess) {
-        (void)hipFree(d);
-        return nullptr;
-    }
-    const uint8_t* hb = (const uint8_t*)host;
-    g_tabs.push_back(Table{dev, std::vector<uint8_t>(hb, hb + bytes), d, false});
-    return d;
-}
+// what the calling thread's last launch() launched: every kernel goes through cext::launch_recorded
+void last_launch(int* route, int* bucket) { cext::last_launch(route, bucket); }
 
 template <int LP>
 static hipError_t launch_fast_lp(const void* x, void* y, int64_t rows, int64_t width, int64_t ow, const int32_t* hq,
@@ -466,14 +381,9 @@ static hipError_t launch_generic(int route, const void* x, void* y, int64_t rows
     if (blocks >= ((int64_t)1 << 31)) return hipErrorInvalidValue;
     const dim3 grid((unsigned)blocks);
     hipError_t e = hipSuccess;
-    std::lock_guard<std::mutex> hold(g_tab_mu);  // until the launch is enqueued
+    std::lock_guard<std::mutex> hold(cext::g_tab_mu);  // until the launch is enqueued
     if (route == FIR_CDECIM_GENERIC32) {
-        std::vector<uint32_t> pk(2 * (size_t)L);
-        for (int k = 0; k < L; ++k) {
-            const uint32_t r16 = (uint32_t)hq[2 * k] & 0xFFFFu, i16 = (uint32_t)hq[2 * k + 1] & 0xFFFFu;
-            pk[2 * (size_t)k] = r16 | (((uint32_t)(-hq[2 * k + 1]) & 0xFFFFu) << 16);
-            pk[2 * (size_t)k + 1] = i16 | (r16 << 16);
-        }
+        const std::vector<uint32_t> pk = cext::pack_dot2(hq, L);
         const uint32_t* pd = (const uint32_t*)table_locked(pk.data(), sizeof(uint32_t) * pk.size(), s, &e);
         if (!pd) return e;
         return launch_recorded(route, 0, fir1d_cplx_decim_generic32_kernel<STAGE>, grid, 0, s, (const uint32_t*)x,
@@ -493,8 +403,7 @@ int launch(const int16_t* x, int64_t rows, int64_t width, const int32_t* hq, int
     int64_t ow = 0;
     const int rc = check(x, y, rows, width, hq, L, decim, phase, frac, acc_bits, stage, &ow, err);
     if (rc) return rc;
-    t_route = FIR_CDECIM_NONE;
-    t_bucket = 0;
+    cext::launch_none();
     if (rows == 0 || ow == 0) return FIR_OK;
     int bucket = 0;
     const int route = route_of((uintptr_t)x, (uintptr_t)y, rows, width, ow, hq, L, decim, frac, acc_bits, stage, &bucket);

@@ -1,0 +1,145 @@
+// cext_launch.h — the host side that the kernel sources of the complex-tap rate-changing FIRs
+// share (fir1d_cplx_decim.hip, fir1d_cplx_interp.hip, fir1d_cplx_resample.hip): the common head of
+// check(), the exactness tests behind the routes, the generic-32 tap packing, the launch record
+// and the generic kernels' tap-table cache.  No library compiles this directory on its own; each
+// includes this header into its one kernel source.  No device code lives here.
+//
+// Everything here has internal linkage (an unnamed namespace, `static`): the libraries are loaded
+// into one process and each keeps its own launch record and table cache.  Nothing `inline` with
+// external linkage may be added: it would become one weak dynamic symbol common to all of them.
+#pragma once
+
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include <cstring>
+#include <mutex>
+#include <string>
+#include <vector>
+
+#include "fir_common.h"
+#include "fir_hip.h"
+
+namespace cext {
+namespace {
+
+// csrc/fir1d.hip's check_fir1d for int16 of two channels and one filter, its order and its texts
+// (tests/test_cabi_c*.py hold them against libfir_hip.so's).  A library's check() starts with this
+// and goes on with its own rate and size checks.
+static int check_head(int64_t rows, int64_t width, const int32_t* hq, int L, int frac, int acc_bits, int stage,
+                      std::string* err) {
+    if (stage != FIR_OUT_U8_SAT && stage != FIR_OUT_I32)
+        return *err = "out_stage must be FIR_OUT_U8_SAT or FIR_OUT_I32", FIR_EINVAL;
+    if (rows < 0 || width < 0) return *err = "rows and width must be >= 0", FIR_EINVAL;
+    if (!hq) return *err = "hq must not be NULL", FIR_EINVAL;
+    if (L < 1 || L > FIR_MAX_TAPS) return *err = "taps must be in [1, " + std::to_string(FIR_MAX_TAPS) + "]", FIR_EINVAL;
+    if (frac < 1 || acc_bits < 1) return *err = "frac_bits and acc_bits must be >= 1", FIR_EINVAL;
+    return FIR_OK;
+}
+
+// 32-bit wrap-around sums over v_dot2_i32_i16 are exact for the call: both tap parts (and -hi) fit
+// in int16, and the wrap and the rounding shift stay inside 32 bits
+static bool dot2_ok(const int32_t* hq, int L, int frac, int acc_bits) {
+    if (acc_bits > 32 || frac > 31) return false;
+    for (int64_t k = 0; k < 2 * (int64_t)L; ++k)
+        if (hq[k] < -32767 || hq[k] > 32767) return false;
+    return true;
+}
+
+// csrc/fir1d.hip's needs_wide for int16 samples over the 2 L tap parts: a no-wrap call whose exact
+// sum could reach 2^63
+static bool needs_wide(const int32_t* hq, int L, int acc_bits) {
+    if (acc_bits < 64) return false;
+    unsigned __int128 habs = 0;
+    for (int64_t k = 0; k < 2 * (int64_t)L; ++k) habs += (unsigned __int128)(hq[k] < 0 ? -(int64_t)hq[k] : (int64_t)hq[k]);
+    return habs * 32768 >= ((unsigned __int128)1 << 63);
+}
+
+// The generic-32 kernels' table: pk[2k] = (hr[k], -hi[k]), pk[2k + 1] = (hi[k], hr[k]), int16 pairs
+static std::vector<uint32_t> pack_dot2(const int32_t* hq, int L) {
+    std::vector<uint32_t> pk(2 * (size_t)L);
+    for (int k = 0; k < L; ++k) {
+        const uint32_t r16 = (uint32_t)hq[2 * k] & 0xFFFFu, i16 = (uint32_t)hq[2 * k + 1] & 0xFFFFu;
+        pk[2 * (size_t)k] = r16 | (((uint32_t)(-hq[2 * k + 1]) & 0xFFFFu) << 16);
+        pk[2 * (size_t)k + 1] = i16 | (r16 << 16);
+    }
+    return pk;
+}
+
+// ---- the launch wrapper: every kernel of a library is launched here, and what was launched is
+// kept for last_launch (this thread).  0 is every library's FIR_*_NONE.
+thread_local int t_route = 0, t_bucket = 0;
+
+// a call that passed its checks: nothing launched yet
+static void launch_none() {
+    t_route = 0;
+    t_bucket = 0;
+}
+
+template <typename... KArgs, typename... Args>
+static hipError_t launch_recorded(int route, int bucket, void (*kernel)(KArgs...), dim3 grid, size_t shmem,
+                                  hipStream_t s, Args... args) {
+    hipLaunchKernelGGL(kernel, grid, dim3(fir::kBlock), shmem, s, (KArgs)args...);
+    const hipError_t e = hipGetLastError();
+    if (e == hipSuccess) {
+        t_route = route;
+        t_bucket = bucket;
+    }
+    return e;
+}
+
+static void last_launch(int* route, int* bucket) {
+    if (route) *route = t_route;
+    if (bucket) *bucket = t_bucket;
+}
+
+// ---- the generic kernels' tap tables: device copies cached per device by the exact bytes they
+// hold, confirmed by comparing them, uploaded once (complete before the call returns).  A caller
+// holds g_tab_mu from the lookup until its launch is enqueued, so when the cached bytes of a
+// device pass kTabCap a device-wide synchronise leaves no launch that reads a table outstanding
+// and the device's tables are freed; a table used inside a stream capture is never freed (the
+// graph may replay it), and nothing is evicted while a capture is under way.
+constexpr size_t kTabCap = size_t(64) << 20;
+struct Table {
+    int dev;
+    std::vector<uint8_t> key;
+    void* d;
+    bool pinned;
+};
+static std::mutex g_tab_mu;
+static std::vector<Table> g_tabs;
+
+static const void* table_locked(const void* host, size_t bytes, hipStream_t s, hipError_t* e) {
+    int dev = 0;
+    if ((*e = hipGetDevice(&dev)) != hipSuccess) return nullptr;
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    const bool capturing = hipStreamIsCapturing(s, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone;
+    size_t held = 0;
+    for (Table& t : g_tabs) {
+        if (t.dev != dev) continue;
+        if (t.key.size() == bytes && std::memcmp(t.key.data(), host, bytes) == 0) {
+            t.pinned |= capturing;
+            return t.d;
+        }
+        held += t.key.size();
+    }
+    if (held && held + bytes > kTabCap && !capturing && hipDeviceSynchronize() == hipSuccess) {
+        for (size_t i = g_tabs.size(); i-- > 0;)
+            if (g_tabs[i].dev == dev && !g_tabs[i].pinned) {
+                (void)hipFree(g_tabs[i].d);
+                g_tabs.erase(g_tabs.begin() + (ptrdiff_t)i);
+            }
+    }
+    void* d = nullptr;
+    if ((*e = hipMalloc(&d, bytes)) != hipSuccess) return nullptr;
+    if ((*e = hipMemcpy(d, host, bytes, hipMemcpyHostToDevice)) != hipSuccess) {
+        (void)hipFree(d);
+        return nullptr;
+    }
+    const uint8_t* hb = (const uint8_t*)host;
+    g_tabs.push_back(Table{dev, std::vector<uint8_t>(hb, hb + bytes), d, false});
+    return d;
+}
+
+}  // namespace
+}  // namespace cext

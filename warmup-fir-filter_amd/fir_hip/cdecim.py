@@ -10,13 +10,12 @@ The C ABI is declared in ``include/fir_cdecim.h``.  The library is an extension 
 from __future__ import annotations
 
 import ctypes
-import threading
-from pathlib import Path
 from typing import NamedTuple
 
 import numpy as np
 
-from . import (OUT_I32, OUT_U8_SAT, FirHipError, _out_buf, _ptr, _share_torch_hip_runtime, _taps_cplx_i32)
+from . import OUT_I32, OUT_U8_SAT, FirHipError, _out_buf, _ptr, _taps_cplx_i32
+from ._ext import Ext, host_rows
 
 __all__ = ["lib", "lib_path", "build_id", "out_width", "route", "last_launch", "fir1d_fixed_rows_cplx_decim",
            "Route", "ROUTE_NONE", "ROUTE_FAST", "ROUTE_GENERIC32", "ROUTE_GENERIC64", "ROUTE_GENERIC128", "EXPORTS"]
@@ -38,9 +37,9 @@ EXPORTS = {
     "fir_cplx_decim_last_launch": (_i32, [_pi32, _pi32]),
 }
 
-_HERE = Path(__file__).resolve().parent
-_lib = None
-_lock = threading.Lock()
+# the loader: libfir_cdecim.so is loaded by the first lib() call, not on import
+_ext = Ext("cdecim", EXPORTS)
+lib, lib_path, build_id, _check = _ext.lib, _ext.lib_path, _ext.build_id, _ext.check
 
 
 class Route(NamedTuple):
@@ -48,55 +47,6 @@ class Route(NamedTuple):
     count (0 off the fast path)."""
     route: int
     tap_bucket: int
-
-
-def lib_path() -> Path:
-    return _HERE / "libfir_cdecim.so"
-
-
-def lib() -> ctypes.CDLL:
-    """Load libfir_cdecim.so once; raise FirHipError if it is missing or built from other sources."""
-    global _lib
-    if _lib is not None:
-        return _lib
-    with _lock:
-        if _lib is not None:
-            return _lib
-        path = lib_path()
-        if not path.exists():
-            raise FirHipError(
-                f"{path} is not built: run `make -C warmup-fir-filter_amd/csrc_cdecim` or "
-                "`python -c 'import __graft_entry__ as g; g.build()'` (hipcc --offload-arch=gfx950)")
-        _share_torch_hip_runtime()
-        try:
-            handle = ctypes.CDLL(str(path))
-        except OSError as exc:
-            raise FirHipError(f"cannot load {path}: {exc}") from exc
-        for name, (res, args) in EXPORTS.items():
-            try:
-                fn = getattr(handle, name)
-            except AttributeError as exc:
-                raise FirHipError(f"{path} does not export {name}") from exc
-            fn.restype = res
-            fn.argtypes = args
-        from ._srcid_cdecim import source_id
-
-        built, want = handle.fir_cdecim_build_id().decode(), source_id()
-        if want is not None and built != want:
-            raise FirHipError(f"{path} was built from other sources (build id {built}, the sources beside it hash "
-                              f"to {want}): rebuild with `make -C warmup-fir-filter_amd/csrc_cdecim`")
-        _lib = handle
-    return _lib
-
-
-def build_id() -> str:
-    return lib().fir_cdecim_build_id().decode()
-
-
-def _check(rc: int, what: str) -> None:
-    if rc != 0:
-        msg = lib().fir_cdecim_last_error().decode(errors="replace")
-        raise FirHipError(f"{what} failed (status {rc}): {msg}")
 
 
 def out_width(width: int, decim: int, phase: int = 0) -> int:
@@ -117,22 +67,14 @@ def route(x_addr: int, y_addr: int, rows: int, width: int, hq, decim: int, phase
     """The kernel a call with these arguments would take (fir_cplx_decim_route): ``x_addr`` and
     ``y_addr`` are the addresses x and y would have, ``rows`` and ``width`` count frames.  Needs no
     device.  ROUTE_NONE for an empty problem; FirHipError for a call the library refuses."""
-    h = _taps_cplx_i32(hq)
-    bucket = ctypes.c_int(0)
-    r = lib().fir_cplx_decim_route(int(x_addr), int(y_addr), int(rows), int(width), _ptr(h), h.shape[0], int(decim),
-                                   int(phase), int(frac_bits), int(acc_bits), int(out_stage), ctypes.byref(bucket))
-    if r < 0:
-        raise FirHipError("fir_cplx_decim_route refused the call: " +
-                          lib().fir_cdecim_last_error().decode(errors="replace"))
-    return Route(r, bucket.value)
+    return Route(*_ext.route("fir_cplx_decim_route", x_addr, y_addr, rows, width, hq, (decim, phase), frac_bits,
+                             acc_bits, out_stage))
 
 
 def last_launch() -> Route:
     """What the calling thread's last fir_cplx_decim_rows[_dev] call that passed its checks
     launched (ROUTE_NONE: nothing)."""
-    r, bucket = ctypes.c_int(0), ctypes.c_int(0)
-    _check(lib().fir_cplx_decim_last_launch(ctypes.byref(r), ctypes.byref(bucket)), "fir_cplx_decim_last_launch")
-    return Route(r.value, bucket.value)
+    return Route(*_ext.last_launch("fir_cplx_decim_last_launch"))
 
 
 def fir1d_fixed_rows_cplx_decim(x: np.ndarray, hq, decim: int, phase: int = 0, frac_bits: int = 12,
@@ -143,16 +85,8 @@ def fir1d_fixed_rows_cplx_decim(x: np.ndarray, hq, decim: int, phase: int = 0, f
     computed in one pass that writes only the kept frames.  x's last axis holds 2 * width interleaved
     int16 (re, im) values, hq is a (taps, 2) integer array of (hr, hi).  Returns x's leading axes with a
     last axis of 2 * out_width(width, decim, phase) values, int32 (OUT_I32) or uint8 (OUT_U8_SAT)."""
-    if not isinstance(x, np.ndarray) or x.dtype != np.int16:
-        raise FirHipError(f"x must be an int16 array of interleaved (re, im), got {getattr(x, 'dtype', type(x).__name__)}")
-    if x.ndim == 0:
-        raise FirHipError("x must have at least one axis of interleaved (re, im) values")
-    if x.shape[-1] % 2:
-        raise FirHipError(f"x's last axis must hold an even number of values (re, im pairs), got {x.shape[-1]}")
-    x = np.ascontiguousarray(x)
+    x, rows, rowlen = host_rows(x)
     h = _taps_cplx_i32(hq)
-    rowlen = x.shape[-1]
-    rows = x.size // rowlen if rowlen else 0
     ow = out_width(rowlen // 2, decim, phase)
     y = _out_buf(out, x.shape[:-1] + (2 * ow,), np.uint8 if out_stage == OUT_U8_SAT else np.int32, x)
     _check(lib().fir_cplx_decim_rows(_ptr(x), rows, rowlen // 2, _ptr(h), h.shape[0], int(decim), int(phase),

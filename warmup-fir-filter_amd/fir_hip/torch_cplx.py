@@ -44,3 +44,23 @@ def fir1d_fixed_rows_cplx_dev(x: torch.Tensor, hq, frac_bits: int = 12, acc_bits
                                    int(acc_bits), int(out_stage), ctypes.c_void_p(out.data_ptr()),
                                    _stream_ptr(x, stream)), "fir_cplx_rows_dev")
     return out
+
+
+def _cplx_rate_dev(ext, entry: str, x: torch.Tensor, hq, rates, frac_bits, acc_bits, out_stage, out, stream) -> torch.Tensor:
+    """The device-tensor entry of a rate-changing complex-tap FIR: ``ext`` is its ctypes module
+    (:mod:`fir_hip.cdecim`, :mod:`fir_hip.cinterp` or :mod:`fir_hip.cresample`), ``entry`` its
+    fir_cplx_*_rows_dev and ``rates`` that entry's rate arguments, in its order and ext.out_width's."""
+    _check_dev(x, "x")
+    if x.dtype != torch.int16:
+        raise FirHipError(f"x dtype must be int16 (interleaved re, im), got {x.dtype}")
+    t = hq if isinstance(hq, CplxTaps) else CplxTaps(hq)
+    rows, rowlen = _rows_of(x, 2)  # a 0-d x counts as a row of one value: refused as an odd row
+    shape = tuple(x.shape[:-1]) + (2 * ext.out_width(rowlen // 2, *rates),)
+    if out is None:
+        out = torch.empty(shape, dtype=_out_dtype(out_stage), device=x.device)
+    _check_out(out, shape, _out_dtype(out_stage), x)
+    _no_overlap([("x", x)], [("out", out)])
+    ext._check(getattr(ext.lib(), entry)(ctypes.c_void_p(x.data_ptr()), rows, rowlen // 2, t.ptr, t.n,
+                                         *(int(v) for v in rates), int(frac_bits), int(acc_bits), int(out_stage),
+                                         ctypes.c_void_p(out.data_ptr()), _stream_ptr(x, stream)), entry)
+    return out
