@@ -1,6 +1,6 @@
 // cext_capi.h — the host layer behind the extern "C" boundary of an extension library
-// (capi_cdecim.hip, capi_cinterp.hip, capi_cresample.hip).  No library compiles this directory on
-// its own; each includes this header into its one capi_*.hip.
+// (capi_cdecim.hip, capi_cinterp.hip, capi_cresample.hip, capi_cstream.hip).  No library compiles
+// this directory on its own; each includes this header into its one capi_*.hip.
 //
 // The host-pointer entry owns, per device, one non-blocking stream and a grow-only pair of device
 // buffers behind a mutex (calls are serialised per device): H2D copy, kernel, D2H copy, stream
@@ -141,6 +141,42 @@ int host_rows(const char* lib, int device, const void* x, void* y, size_t in_byt
         return fail(rc, err);
     }
     const hipError_t e = hipMemcpyAsync(y, st->out.ptr, out_bytes, hipMemcpyDeviceToHost, st->stream);
+    const hipError_t es = hipStreamSynchronize(st->stream);
+    if (e != hipSuccess) return fail(FIR_EHIP, std::string("hipMemcpyAsync (D2H): ") + hipGetErrorString(e));
+    if (es != hipSuccess) return fail(FIR_EHIP, std::string("hipStreamSynchronize: ") + hipGetErrorString(es));
+    return FIR_OK;
+}
+
+// The same for an entry that moves two inputs and two outputs (capi_cstream.hip: a block and its
+// history in, the kept frames and the next history out).  Either second pointer may be NULL: that
+// array is not moved and launch gets NULL for it.  The second array of each pair sits in the same
+// device buffer as the first, at the next multiple of 256 bytes.
+template <typename Launch>
+int host_rows2(const char* lib, int device, const void* x, size_t in_bytes, const void* x2, size_t in2_bytes, void* y,
+               size_t out_bytes, void* y2, size_t out2_bytes, Launch launch) {
+    int rc;
+    DeviceRestore restore;
+    DeviceState* st = nullptr;
+    if ((rc = device_state(device, &st))) return rc;
+    std::lock_guard<std::mutex> lk(st->mu);
+    if ((rc = init_locked(st, device, lib))) return rc;
+    const size_t in2_at = (in_bytes + 255) / 256 * 256, out2_at = (out_bytes + 255) / 256 * 256;
+    if ((rc = ensure(st->in, in2_at + (x2 ? in2_bytes : 0))) || (rc = ensure(st->out, out2_at + (y2 ? out2_bytes : 0))))
+        return rc;
+    char* const in2 = x2 ? (char*)st->in.ptr + in2_at : nullptr;
+    char* const out2 = y2 ? (char*)st->out.ptr + out2_at : nullptr;
+    if (in_bytes) HIP_TRY(hipMemcpyAsync(st->in.ptr, x, in_bytes, hipMemcpyHostToDevice, st->stream));
+    if (in2 && in2_bytes) HIP_TRY(hipMemcpyAsync(in2, x2, in2_bytes, hipMemcpyHostToDevice, st->stream));
+    std::string err;
+    rc = launch((const int16_t*)st->in.ptr, (const int16_t*)in2, st->out.ptr, (int16_t*)out2, st->stream, &err);
+    if (rc) {  // what is already queued must finish first: the next call reuses the buffers
+        (void)hipStreamSynchronize(st->stream);
+        return fail(rc, err);
+    }
+    hipError_t e = hipSuccess;
+    if (out_bytes) e = hipMemcpyAsync(y, st->out.ptr, out_bytes, hipMemcpyDeviceToHost, st->stream);
+    if (e == hipSuccess && out2 && out2_bytes)
+        e = hipMemcpyAsync(y2, out2, out2_bytes, hipMemcpyDeviceToHost, st->stream);
     const hipError_t es = hipStreamSynchronize(st->stream);
     if (e != hipSuccess) return fail(FIR_EHIP, std::string("hipMemcpyAsync (D2H): ") + hipGetErrorString(e));
     if (es != hipSuccess) return fail(FIR_EHIP, std::string("hipStreamSynchronize: ") + hipGetErrorString(es));

@@ -1,5 +1,6 @@
 // cext_launch.h — the host side that the kernel sources of the complex-tap rate-changing FIRs
-// share (fir1d_cplx_decim.hip, fir1d_cplx_interp.hip, fir1d_cplx_resample.hip): the common head of
+// share (fir1d_cplx_decim.hip, fir1d_cplx_interp.hip, fir1d_cplx_resample.hip,
+// fir1d_cplx_stream.hip): the common head of
 // check(), the exactness tests behind the routes, the generic-32 tap packing, the launch record
 // and the generic kernels' tap-table cache.  No library compiles this directory on its own; each
 // includes this header into its one kernel source.  No device code lives here.

@@ -10,7 +10,8 @@ Host-array entry points (NumPy in, NumPy out, synchronous):
     fir1d_fixed_rows_cplx, fir1d_fixed_rows_cplx_decim (the extension library libfir_cdecim.so, loaded on
     first use by :mod:`fir_hip.cdecim`), fir1d_fixed_rows_cplx_interp (libfir_cinterp.so, loaded on first use by
     :mod:`fir_hip.cinterp`), fir1d_fixed_rows_cplx_resample (libfir_cresample.so, loaded on first use by
-    :mod:`fir_hip.cresample`), fir1d_fixed_rows_multi,
+    :mod:`fir_hip.cresample`), fir1d_fixed_rows_cplx_decim_block (libfir_cstream.so, loaded on first use by
+    :mod:`fir_hip.cstream`), fir1d_fixed_rows_multi,
     fir1d_fixed_rows_sharded, fir2d_fixed, fir2d_ideal, fir1d_ideal_rows, compare_metrics, restore_u8, and the stage drivers' image batches
     fir1d_fixed_images_multi / fir1d_ideal_images_multi (page-locked staging: host_empty)
 Device entry points (torch tensors on a HIP device, enqueued on the current stream):
@@ -37,7 +38,7 @@ __all__ = [
     "fir1d_ideal_images_multi", "host_empty", "TIMING_KEYS", "decim_out_width", "fir1d_fixed_rows_decim",
     "interp_out_width", "fir1d_fixed_rows_interp", "resample_out_width", "fir1d_fixed_rows_resample",
     "fir1d_fixed_rows_cplx", "fir1d_fixed_rows_cplx_decim", "fir1d_fixed_rows_cplx_interp", "Launch", "launch_log",
-    "kernel_census", "fir1d_fixed_rows_cplx_resample",
+    "kernel_census", "fir1d_fixed_rows_cplx_resample", "fir1d_fixed_rows_cplx_decim_block",
 ]
 
 IN_U8, IN_I16 = 0, 1
@@ -637,6 +638,17 @@ def fir1d_fixed_rows_cplx_resample(x: np.ndarray, hq, up: int, decim: int, phase
     from . import cresample
 
     return cresample.fir1d_fixed_rows_cplx_resample(x, hq, up, decim, phase, frac_bits, acc_bits, out_stage, device, out)
+
+
+def fir1d_fixed_rows_cplx_decim_block(x: np.ndarray, hist, hq, decim: int, phase: int = 0, frac_bits: int = 12,
+                                      acc_bits: int = 32, out_stage: int = OUT_I32, device: int = 0):
+    """One block of a stream through the causal decimating complex-tap FIR, behind the history that
+    precedes it; returns (y, hist_out, next_phase):
+    :func:`fir_hip.cstream.fir1d_fixed_rows_cplx_decim_block`, whose extension library
+    (libfir_cstream.so) is loaded on first use."""
+    from . import cstream
+
+    return cstream.fir1d_fixed_rows_cplx_decim_block(x, hist, hq, decim, phase, frac_bits, acc_bits, out_stage, device)
 
 
 def fir1d_fixed_rows_sharded(x: np.ndarray, hq, frac_bits: int = 12, acc_bits: int = 32,

@@ -1,7 +1,7 @@
 """The loader the extension libraries' ctypes modules share (:mod:`fir_hip.cdecim`,
-:mod:`fir_hip.cinterp`, :mod:`fir_hip.cresample`): one :class:`Ext` per library, built from its name
+:mod:`fir_hip.cinterp`, :mod:`fir_hip.cresample`, :mod:`fir_hip.cstream`): one :class:`Ext` per library, built from its name
 and its EXPORTS table.  It loads ``libfir_<name>.so`` on first use, binds and checks the exports,
-refuses a library built from other sources, and holds what the three modules' ``route``,
+refuses a library built from other sources, and holds what the modules' ``route``,
 ``last_launch`` and host-array entries have in common.  Constructing one loads nothing.
 """
 from __future__ import annotations
@@ -75,6 +75,18 @@ class Ext:
         h = _taps_cplx_i32(hq)
         bucket = ctypes.c_int(0)
         r = getattr(self.lib(), entry)(int(x_addr), int(y_addr), int(rows), int(width), _ptr(h), h.shape[0],
+                                       *(int(v) for v in rates), int(frac_bits), int(acc_bits), int(out_stage),
+                                       ctypes.byref(bucket))
+        if r < 0:
+            raise FirHipError(f"{entry} refused the call: " + self.last_error())
+        return r, bucket.value
+
+    def route4(self, entry: str, addrs, rows, width, hq, rates, frac_bits, acc_bits, out_stage) -> tuple[int, int]:
+        """:meth:`route` for an entry that takes four addresses (fir_cplx_stream_route: x, hist_in, y
+        and hist_out, 0 for NULL)."""
+        h = _taps_cplx_i32(hq)
+        bucket = ctypes.c_int(0)
+        r = getattr(self.lib(), entry)(*(int(a) for a in addrs), int(rows), int(width), _ptr(h), h.shape[0],
                                        *(int(v) for v in rates), int(frac_bits), int(acc_bits), int(out_stage),
                                        ctypes.byref(bucket))
         if r < 0:
