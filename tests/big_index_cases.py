@@ -29,6 +29,15 @@ resample_path_ok, cplx_path_ok here; reg_path_ok, mfma_path_ok and the k-step co
 launch_mfma_t, lds_path_ok and the register test of launch_fir1d_ideal in
 tests/fullrate_property_cases.py, which states them once); ``Case.kernel`` is the kernel each
 large case was built for, and the two must agree before a case runs.
+
+The four complex-rate extension libraries (families ``cdecim``, ``cinterp``, ``cresample`` and
+``cstream``: complex int16 frames, one dword in and an int32 pair out) write nothing to the launch
+log; their ``Case.kernel`` is the (route, bucket) of the library's own record as a string such as
+``"cdecim:FAST/12"``, and ``dispatch_kernel`` gives the ``predicted_route`` of the family's
+``*_cases.py`` helper in that form.  A ``cstream`` case is one block behind a hostile history
+(``make_hist``; row r has history r % Q, so the rows still repeat with Q): its y is checked like
+every other family's (the filter is causal, so from period 1 on the output has period P), and
+``verify`` holds hist_out against the last taps - 1 frames of every row of x.
 """
 from __future__ import annotations
 
@@ -38,8 +47,13 @@ from typing import Callable
 import numpy as np
 import torch
 
+import cdecim_cases
+import cinterp_cases
 import cplx_ref
+import cresample_cases
+import cstream_cases
 import fir_hip
+from fir_hip import cdecim, cinterp, cresample, cstream
 from oracle import c_oracle
 from fullrate_property_cases import Case as FullRateCase
 from fullrate_property_cases import _mfma_ksteps, bank_fused, ideal_kernel, rows_kernel  # noqa: F401  (_mfma_ksteps: re-exported)
@@ -53,6 +67,9 @@ CAP_BYTES = 24 * GIB          # x + y + compare temporaries of one case
 TEMP_BYTES = 1 * GIB          # the compare temporaries' share of it
 CHUNK = 1 << 28               # elements compared at once: a bool and a uint8 temporary of 256 MiB each
 FILL = 1 << 26                # elements of the tiled block x is filled from
+CEXT = {"cdecim": (cdecim, cdecim_cases), "cinterp": (cinterp, cinterp_cases), "cresample": (cresample, cresample_cases),
+        "cstream": (cstream, cstream_cases)}  # family: (the library's ctypes module, its test helper)
+ROUTES = ("NONE", "FAST", "GENERIC32", "GENERIC64", "GENERIC128")  # FIR_C*_NONE .. _GENERIC128
 
 
 @dataclass(frozen=True)
@@ -73,10 +90,12 @@ SMALL = Scale(lambda e: 1 << 12, 101, 13, 64)  # the CPU self-test: 2^12 for eve
 class Case:
     """One call.  width: input frames per row.  x_off: elements x starts past a 16-byte boundary.
     crosses: (side, unit, exponent) claims, e.g. ("out", "byte", 33): the output's bytes pass
-    thr(33).  kernel: the kernel the case was built for (None for a twin: whatever dispatch_kernel
+    thr(33); units are elem, byte and frame (ch elements), sides in, out, "stuffed" (the resampler's
+    zero-stuffed index m * D + phase, which reaches width * U) and "hist" (a stream's rows * H history
+    frames).  kernel: the kernel the case was built for (None for a twin: whatever dispatch_kernel
     says)."""
     name: str
-    family: str          # fixed | bank | ideal | decim | interp | resample | cplx
+    family: str          # fixed | bank | ideal | decim | interp | resample | cplx | cdecim | cinterp | cresample | cstream
     dtype: str           # u8 | i16
     stage: int | None    # U8 | I32; None: the float64 ideal model
     ch: int
@@ -111,6 +130,12 @@ class Case:
             return fir_hip.interp_out_width(self.width, self.up)
         if self.family == "resample":
             return fir_hip.resample_out_width(self.width, self.up, self.decim, self.phase)
+        if self.family in ("cdecim", "cstream"):
+            return CEXT[self.family][0].out_width(self.width, self.decim, self.phase)
+        if self.family == "cinterp":
+            return cinterp.out_width(self.width, self.up)
+        if self.family == "cresample":
+            return cresample.out_width(self.width, self.up, self.decim, self.phase)
         return self.width
 
     @property
@@ -121,14 +146,25 @@ class Case:
     def out_elems(self) -> int:
         return self.filters * self.rows * self.out_width * self.ch
 
+    @property
+    def hist_frames(self) -> int:
+        """H: the frames of history a stream's block reads and writes per row (0: not a stream)."""
+        return self.taps - 1 if self.family == "cstream" else 0
+
     def size(self, side: str, unit: str) -> int:
-        n = self.in_elems if side == "in" else self.out_elems
-        return n * (1 if unit == "elem" else (self.in_itemsize if side == "in" else self.out_itemsize))
+        n = {"in": self.in_elems, "out": self.out_elems, "stuffed": self.in_elems * self.up,
+             "hist": self.rows * self.hist_frames * self.ch}[side]
+        if unit == "frame":
+            return n // self.ch
+        return n * (1 if unit == "elem" else (self.out_itemsize if side == "out" else self.in_itemsize))
 
     @property
     def footprint(self) -> int:
-        """Device bytes of the case: x (with the slack an offset x is cut from), y, the temporaries."""
-        return (self.in_elems + 16) * self.in_itemsize + self.out_elems * self.out_itemsize + TEMP_BYTES
+        """Device bytes of the case: x (with the slack an offset x is cut from), y, the temporaries;
+        a stream's two histories, hist_out inside its guards (tests/guarded.py: 64 KiB and two rows
+        a side, rounded up: 1 MiB covers them)."""
+        hist = 2 * self.size("hist", "byte") + (1 << 20) if self.hist_frames else 0
+        return (self.in_elems + 16) * self.in_itemsize + self.out_elems * self.out_itemsize + hist + TEMP_BYTES
 
     @property
     def period(self) -> int:
@@ -156,11 +192,11 @@ class Case:
 def taps_of(c: Case):
     """The case's taps from its seed.  Real fixed taps: L ints whose sum is about U * 2^FRAC, so a
     u8 stage spreads over its range instead of saturating (a displaced tile must not meet a row of
-    255s); bank: filters x L; ideal: L doubles; cplx: L (hr, hi) pairs."""
+    255s); bank: filters x L; ideal: L doubles; cplx and the complex-rate families: L (hr, hi) pairs."""
     rng = np.random.default_rng(c.seed)
     if c.family == "ideal":
         return rng.uniform(-1.0, 1.0, c.taps)
-    if c.family == "cplx":
+    if c.family == "cplx" or c.family in CEXT:
         return rng.integers(-2000, 2001, (c.taps, 2))
     h = rng.integers(50, 1200, (c.filters, c.taps)).astype(np.float64)
     h[:, 1::3] *= -0.25  # some negative taps; the sum stays well above zero
@@ -247,6 +283,41 @@ def table(s: Scale = FULL) -> list[Case]:
     add("cplx_65_generic", "cplx", "i16", I32, 2, 65, thr(30) + pad, kernel="fir1d_cplx_generic32_kernel",
         crosses=(("in", "elem", 31), ("in", "byte", 32), ("out", "byte", 33)))
 
+    # the complex-rate extension libraries: complex int16 frames (one dword in, an int32 pair out).
+    # fast: x at a 16-byte boundary; generic32: x 4 bytes off it; generic64: x 2 bytes off it.
+    def cext(name, family, route, taps, width, *, x_off=0, **kw):
+        add(name, family, "i16", I32, 2, taps, width, kernel=f"{family}:{route}", x_off=x_off, **kw)
+
+    def fast_and_g32(name, family, bucket, taps, width, **kw):
+        cext(name + "_fast", family, f"FAST/{bucket}", taps, width, **kw)
+        cext(name + "_generic32", family, "GENERIC32/0", taps, width, x_off=2, **kw)
+
+    many = thr(31) // W + 3        # rows of W frames whose r * width passes thr(31) frames
+    d2 = (("in", "frame", 31), ("in", "byte", 33), ("out", "elem", 31), ("out", "byte", 33))
+    fast_and_g32("cdecim_D2", "cdecim", 12, 9, thr(31) + pad, decim=2, phase=1, crosses=d2)
+    cext("cdecim_D2_g64", "cdecim", "GENERIC64/0", 9, thr(30) + pad, x_off=1, decim=2, phase=0,
+         crosses=(("in", "elem", 31), ("in", "byte", 32), ("out", "byte", 32)))
+    cext("cdecim_D16_fast", "cdecim", "FAST/64", 64, thr(32) + pad, decim=16, phase=15,
+         crosses=(("in", "frame", 32), ("in", "byte", 34)))
+    cext("cdecim_rows_fast", "cdecim", "FAST/16", 16, W, rows=many, decim=3, phase=2, crosses=(("in", "frame", 31),))
+    # rows of W + 2 frames: every other row starts 8 bytes off a 16-byte boundary, which the fast kernel does not take
+    cext("cdecim_rows_generic32", "cdecim", "GENERIC32/0", 16, W + 2, rows=many, decim=3, phase=2,
+         crosses=(("in", "frame", 31),))
+    fast_and_g32("cinterp_U16", "cinterp", 4, 64, thr(27) + pad, up=16,
+                 crosses=(("out", "frame", 31), ("out", "elem", 32), ("out", "byte", 34)))
+    cext("cinterp_U2_fast", "cinterp", "FAST/6", 9, thr(30) + pad, up=2,
+         crosses=(("in", "elem", 31), ("in", "byte", 32), ("out", "frame", 31)))
+    cext("cinterp_rows_fast", "cinterp", "FAST/4", 16, W, rows=thr(17) + 3, up=4, crosses=(("out", "frame", 31),))
+    fast_and_g32("cresample_3_2", "cresample", 24, 72, up_to(2 * thr(31), 3) + pad, up=3, decim=2, phase=1,
+                 crosses=(("out", "frame", 31), ("out", "byte", 34), ("in", "byte", 32)))
+    fast_and_g32("cresample_2_3", "cresample", 6, 9, thr(31) + pad, up=2, decim=3, phase=2,
+                 crosses=(("in", "frame", 31), ("stuffed", "frame", 32), ("out", "elem", 31)))
+    cext("cresample_rows_fast", "cresample", "FAST/8", 16, W, rows=many, up=2, decim=3, phase=1,
+         crosses=(("in", "frame", 31),))
+    fast_and_g32("cstream_D2", "cstream", 48, 33, thr(31) + pad, decim=2, phase=1, crosses=d2)
+    cext("cstream_rows_fast", "cstream", "FAST/64", 64, W, rows=many, decim=3, phase=2,
+         crosses=(("in", "frame", 31), ("hist", "frame", 24)))
+
     out = []
     for c in big:
         out.append(c)
@@ -256,10 +327,31 @@ def table(s: Scale = FULL) -> list[Case]:
 
 
 # ---- dispatch, restated ------------------------------------------------------------------------------
-def dispatch_kernel(c: Case, x_ptr: int, y_ptr: int) -> str:
+def rate_args(c: Case) -> tuple:
+    """The rate arguments of a complex-rate family's entry, route query and predicted_route, in their order."""
+    return {"cdecim": (c.decim, c.phase), "cinterp": (c.up,), "cresample": (c.up, c.decim, c.phase),
+            "cstream": (c.decim, c.phase)}[c.family]
+
+
+def route_name(family: str, route) -> str:
+    """A library's (route, bucket) in the form of Case.kernel, e.g. "cdecim:FAST/12"."""
+    return f"{family}:{ROUTES[route[0]]}/{route[1]}"
+
+
+def cext_addrs(c: Case, x_ptr: int, y_ptr: int, hist_in_ptr: int = 0, hist_out_ptr: int = 0) -> tuple:
+    """The address arguments of the family's route query: x and y, a stream's two histories between them."""
+    return (x_ptr, hist_in_ptr, y_ptr, hist_out_ptr) if c.family == "cstream" else (x_ptr, y_ptr)
+
+
+def dispatch_kernel(c: Case, x_ptr: int, y_ptr: int, hist_in_ptr: int = 4096, hist_out_ptr: int = 8192) -> str:
     """The kernel csrc launches for the case with x and y at these addresses.  The full-rate
     (``fixed``, ``bank``) and ``ideal`` branches are tests/fullrate_property_cases.py's restatement
-    (rows_kernel, bank_fused, ideal_kernel), stated once there."""
+    (rows_kernel, bank_fused, ideal_kernel), stated once there; a complex-rate family's is its
+    helper's predicted_route (a stream's histories at the two further addresses)."""
+    if c.family in CEXT:
+        pred = CEXT[c.family][1].predicted_route(*cext_addrs(c, x_ptr, y_ptr, hist_in_ptr, hist_out_ptr), c.rows, c.width,
+                                                 taps_of(c), *rate_args(c), FRAC, ACC, c.stage)
+        return route_name(c.family, pred)
     u8 = c.dtype == "u8"
     rows, ch, L = c.rows, c.ch, c.taps
     h = np.asarray(taps_of(c) if c.family != "ideal" else [0], dtype=np.int64).reshape(-1)
@@ -337,11 +429,42 @@ def make_y(c: Case, device) -> torch.Tensor:
     return y.view(((c.filters,) if c.family == "bank" else ()) + row)
 
 
+def hist_base(c: Case) -> np.ndarray:
+    """The histories a stream's hist_in is tiled from: (1, 2 H), or (Q, 2 H) for a many-rows case."""
+    return cstream_cases.hostile_history(np.random.default_rng(c.seed + 2), c.Q if c.rows > 1 else 1, c.hist_frames)
+
+
+def hist_rows(c: Case, r0: int = 0, r1: int = 1):
+    """hist_in of rows r0 .. r1 - 1 as a (r1 - r0, 2 H) array (row r has history r % Q); None for
+    a family without one."""
+    if not c.hist_frames:
+        return None
+    base = hist_base(c)
+    return base[np.arange(r0, r1) % base.shape[0]]
+
+
+def make_hist(c: Case, device) -> torch.Tensor:
+    """A stream's hist_in on ``device``: (2 H,) for one row, else (rows, 2 H)."""
+    base = torch.from_numpy(hist_base(c)).to(device)
+    if c.rows == 1:
+        return base.reshape(-1).clone()
+    return base.repeat(-(-c.rows // c.Q), 1)[:c.rows].contiguous()
+
+
 # ---- the references ------------------------------------------------------------------------------------
-def reference(c: Case, x: np.ndarray) -> np.ndarray:
+def reference(c: Case, x: np.ndarray, hist: np.ndarray | None = None) -> np.ndarray:
     """What the family's entry must give for the (rows, width' * ch) array x: (rows, out_width' * ch),
-    a bank (filters, rows, ...); the references of the families' own GPU tests."""
+    a bank (filters, rows, ...); the references of the families' own GPU tests.  hist: a stream's
+    (rows, 2 H) history before x (None: zeros)."""
     h = taps_of(c)
+    if c.family == "cdecim":
+        return cdecim_cases.want(x, h, c.decim, c.phase, FRAC, ACC, c.stage)
+    if c.family == "cinterp":
+        return cinterp_cases.want(x, h, c.up, FRAC, ACC, c.stage)
+    if c.family == "cresample":
+        return cresample_cases.want(x, h, c.up, c.decim, c.phase, FRAC, ACC, c.stage)
+    if c.family == "cstream":
+        return cstream_cases.want_block(x, hist, h, c.decim, c.phase, FRAC, ACC, c.stage)[0]
     o = c_oracle()
     if c.family == "fixed":
         return o.fir1d_rows(x, h, FRAC, ACC, c.stage, channels=c.ch)
@@ -375,14 +498,16 @@ def input_span(c: Case, out_lo: int, out_hi: int) -> tuple[int, int, int]:
 
 # ---- the comparisons -------------------------------------------------------------------------------------
 class Mismatch(AssertionError):
-    """verify's finding: .step ("periods" | "rows" | "band"), .index (the first differing output
-    element), .frame (its output frame, counted from the tensor's start) and .count."""
+    """verify's finding: .step ("periods" | "rows" | "band" | "hist"), .index (the first differing
+    output element; of hist_out for "hist"), .frame (its frame, counted from the tensor's start) and
+    .count."""
 
     def __init__(self, c: Case, step: str, index: int, count: int, of: int, detail: str = ""):
         self.step, self.index, self.count = step, index, count
         self.frame = index // c.ch
-        super().__init__(f"{c.name} [{step}]: {count} of {of} compared outputs differ{detail}; the first is output "
-                         f"frame {self.frame} (element {index}, byte offset {index * c.out_itemsize:#x})")
+        what, itemsize = ("hist_out", c.in_itemsize) if step == "hist" else ("output", c.out_itemsize)
+        super().__init__(f"{c.name} [{step}]: {count} of {of} compared {what} values differ{detail}; the first is {what} "
+                         f"frame {self.frame} (element {index}, byte offset {index * itemsize:#x})")
 
 
 def _bits(t: torch.Tensor) -> torch.Tensor:
@@ -466,7 +591,7 @@ def compare_bands(c: Case, x: torch.Tensor, y: torch.Tensor) -> None:
         spans = [(0, c.rows)] if c.rows <= 2 * c.Q else [(0, c.Q), (c.rows - c.Q, c.rows)]
         y3 = y.reshape(c.filters, c.rows, We)
         for r0, r1 in spans:
-            want = reference(c, _host(x[r0:r1])).reshape(c.filters, r1 - r0, We)
+            want = reference(c, _host(x[r0:r1]), hist_rows(c, r0, r1)).reshape(c.filters, r1 - r0, We)
             for f in range(c.filters):
                 _band_diff(c, _host(y3[f, r0:r1]), want[f], (f * c.rows + r0) * We, f"rows {r0} .. {r1 - 1}")
         return
@@ -476,16 +601,30 @@ def compare_bands(c: Case, x: torch.Tensor, y: torch.Tensor) -> None:
     xf, yf = x.reshape(-1), y.reshape(-1)
     for out_lo, out_hi in spans:
         lo, hi, q = input_span(c, out_lo, out_hi)
-        want = reference(c, _host(xf[lo * c.ch:hi * c.ch]).reshape(1, -1)).reshape(-1)
+        # a stream's slice from frame 0 has the row's history before it; a later one a lead-in that is thrown away
+        want = reference(c, _host(xf[lo * c.ch:hi * c.ch]).reshape(1, -1), hist_rows(c) if lo == 0 else None).reshape(-1)
         _band_diff(c, _host(yf[out_lo * c.ch:out_hi * c.ch]), want[(out_lo - q) * c.ch:(out_hi - q) * c.ch],
                    out_lo * c.ch, f"output frames {out_lo} .. {out_hi - 1} from input frames {lo} .. {hi - 1}")
 
 
-def verify(c: Case, x: torch.Tensor, y: torch.Tensor, chunk: int = CHUNK) -> None:
+def compare_hist(c: Case, x: torch.Tensor, hist_out: torch.Tensor) -> None:
+    """A stream's hist_out against the last H frames of every row of x, bit for bit, on the device
+    (every case here has rows of H frames and more, so none of hist_in remains in it)."""
+    He = c.hist_frames * c.ch
+    assert c.width >= c.hist_frames and hist_out.numel() == c.rows * He <= CHUNK
+    n, i = _diff(hist_out.reshape(c.rows, He), x.reshape(c.rows, -1)[:, c.width * c.ch - He:])
+    if n:
+        raise Mismatch(c, "hist", i, n, c.rows * He, f" from the last {c.hist_frames} frames of x (row {i // He})")
+
+
+def verify(c: Case, x: torch.Tensor, y: torch.Tensor, chunk: int = CHUNK, hist_out: torch.Tensor | None = None) -> None:
     """Steps 3 and 4 on the entry's output y for the input x; raises Mismatch.  The bands go first:
     period 1 and rows 0 .. Q-1 are what step 3 compares everything else with, so an error there is
-    named where it is and not where its first copy was expected."""
+    named where it is and not where its first copy was expected.  A stream's hist_out is held
+    against x between the two."""
     compare_bands(c, x, y)
+    if c.hist_frames:
+        compare_hist(c, x, hist_out)
     if c.rows > 1:
         compare_rows(c, y, chunk)
     else:

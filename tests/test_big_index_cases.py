@@ -9,10 +9,16 @@ the first output that differs.  The full-size table is held to what it claims: e
 the stated threshold on the stated side, every footprint is within the cap, and the dispatch
 conditions restated in ``dispatch_kernel`` (whose constants are read back from csrc) send every
 case to the kernel it was built for.
+
+The complex-rate families (cdecim, cinterp, cresample, cstream) are held to the same checks; their
+routes are the ``predicted_route`` of tests/c*_cases.py (whose constants are read back from
+csrc_c*/ and csrc_cext/) and the libraries' own route query, and a stream's hist_out is part of
+``verify``: a wrong frame planted in it, and a hist_in copied through, are rejected where they are.
 """
 from __future__ import annotations
 
 import re
+from dataclasses import replace
 from pathlib import Path
 
 import numpy as np
@@ -68,14 +74,36 @@ def test_dispatch_sends_the_case_to_its_kernel(c):
     assert bic.dispatch_kernel(c, x_ptr, y_ptr) == c.kernel
     if c.x_off:  # the offset is the only reason the case is off the fast kernel
         assert bic.dispatch_kernel(c, 4096, y_ptr) != c.kernel
+    if c.family in bic.CEXT:
+        lib, helper = bic.CEXT[c.family]
+        args = (c.rows, c.width, bic.taps_of(c), *bic.rate_args(c), bic.FRAC, bic.ACC, c.stage)
+        for ptr in (x_ptr, 4096):  # the library's own route query (it needs no device) says the same
+            addrs = bic.cext_addrs(c, ptr, y_ptr, 4096, 8192)
+            assert tuple(lib.route(*addrs, *args)) == helper.predicted_route(*addrs, *args)
+        if c.x_off:  # ... and at a 16-byte boundary the same call takes the fast kernel
+            assert bic.dispatch_kernel(c, 4096, y_ptr).startswith(c.family + ":FAST/")
+        elif "GENERIC" in c.kernel:  # cdecim_rows_generic32: the row length alone keeps it off
+            assert c.rows > 1 and c.width % 4 == 2
+            assert bic.dispatch_kernel(replace(c, width=c.width - 2), 4096, y_ptr).startswith(c.family + ":FAST/")
 
 
 def test_every_kernel_family_of_the_issue_is_in_the_table():
-    assert {c.kernel for c in FULL_TABLE[0::2]} == {
+    assert {c.kernel for c in FULL_TABLE[0::2] if c.family not in bic.CEXT} == {
         "fir1d_reg_kernel", "fir1d_mfma_step_kernel", "fir1d_mfma_run_kernel", "fir1d_mfma_long_kernel",
         "fir1d_lds_kernel", "fir1d_generic_kernel", "fir1d_ideal_reg_kernel", "fir1d_decim_kernel",
         "fir1d_decim_generic_kernel", "fir1d_interp_kernel", "fir1d_interp_generic_kernel", "fir1d_resample_kernel",
         "fir1d_resample_generic_kernel", "fir1d_cplx_kernel", "fir1d_cplx_generic32_kernel"}
+    # the complex-rate libraries: the fast and the 32-bit generic kernel of each, in one row and in many
+    # rows; the 64-bit generic kernel once (its text is one template in every library)
+    routes = {(c.family, c.kernel.split(":")[1].split("/")[0], c.rows > 1) for c in FULL_TABLE[0::2] if c.family in bic.CEXT}
+    assert routes == {(f, r, False) for f in bic.CEXT for r in ("FAST", "GENERIC32")} | {(f, "FAST", True) for f in bic.CEXT} | {
+        ("cdecim", "GENERIC64", False), ("cdecim", "GENERIC32", True)}
+    by = {c.name: c for c in FULL_TABLE}
+    for name, rows in (("cdecim_rows_fast", (1 << 19) + 3), ("cinterp_rows_fast", (1 << 17) + 3),
+                       ("cresample_rows_fast", (1 << 19) + 3), ("cstream_rows_fast", (1 << 19) + 3)):
+        assert (by[name].rows, by[name].width) == (rows, 4096)
+    assert by["cstream_rows_fast"].hist_frames == 63 and by["cstream_D2_fast"].hist_frames == 32
+    assert by["cresample_2_3_fast"].width * 2 > 1 << 32 and by["cdecim_D16_fast"].width > 1 << 32
 
 
 def test_dispatch_constants_are_the_sources():
@@ -98,20 +126,71 @@ def test_dispatch_constants_are_the_sources():
     assert bic._mfma_ksteps(65) == 3 and bic._mfma_ksteps(66) == 4 and bic._mfma_ksteps(16) == 2
 
 
+def test_complex_rate_constants_are_the_sources():
+    """The numbers the predicted_route of tests/c*_cases.py rest on, read back from csrc_c*/."""
+    import cdecim_cases as dc
+    import cinterp_cases as ci
+    import cresample_cases as cr
+    import cstream_cases as sc
+
+    want = {"csrc_cdecim/fir1d_cplx_decim.hip": {"kCdT": dc.T, "kCdMaxD": dc.MAX_D, "kCdMaxTaps": dc.MAX_TAPS, "kCdChunk": dc.ROW_UNIT},
+            "csrc_cstream/fir1d_cplx_stream.hip": {"kCsT": sc.T, "kCsMaxD": sc.MAX_D, "kCsMaxTaps": sc.MAX_TAPS, "kCsChunk": sc.ROW_UNIT},
+            "csrc_cinterp/fir1d_cplx_interp.hip": {"kCiF": ci.F, "kCiMinT": 256, "kCiOutBytes": 16384, "kCiMaxU": ci.MAX_U,
+                                                   "kCiMaxTaps": ci.MAX_TAPS, "kCiMaxPerPhase": ci.MAX_PER_PHASE,
+                                                   "kCiMaxNP": ci.BUCKETS[-1], "kCiChunk": ci.ROW_UNIT},
+            "csrc_cresample/fir1d_cplx_resample.hip": {"kCrInBytes": 4096, "kCrMinT": 256, "kCrOutBytes": 16384,
+                                                       "kCrMaxUD": cr.MAX_UD, "kCrMaxTaps": cr.MAX_TAPS,
+                                                       "kCrMaxNP": cr.MAX_PER_PHASE, "kCrChunk": cr.ROW_UNIT},
+            "csrc/fir_common.h": {"kBlock": ci.PASS, "kWave": dc.W}}
+    assert (dc.T, dc.MAX_D, dc.MAX_TAPS, dc.ROW_UNIT, dc.W) == (512, 16, 64, 4, 64) and cr.PASS == ci.PASS == 256
+    assert (ci.F, ci.MAX_U, ci.MAX_TAPS, ci.MAX_PER_PHASE, cr.MAX_UD, cr.MAX_TAPS, cr.MAX_PER_PHASE) == (2048, 16, 128, 32, 16, 128, 32)
+    texts = {}
+    for name, consts in want.items():
+        texts[name] = text = (CSRC.parent / name).read_text()
+        for k, v in consts.items():
+            m = re.search(rf"\b{k} = (\d+)\b", text)
+            assert m and int(m.group(1)) == v, (name, k, m and m.group(1))
+        if name.startswith("csrc_c"):  # the width limit of every fast route
+            assert "width < ((int64_t)1 << 40)" in text and "rows <= (((int64_t)1 << 31) - 1) / " in text, name
+    # the tap and window buckets
+    for name in ("csrc_cdecim/fir1d_cplx_decim.hip", "csrc_cstream/fir1d_cplx_stream.hip"):
+        assert "{2, 4, 6, 8, 12, 16, 24, 32, 48}" in texts[name] and dc.BUCKETS == sc.BUCKETS == (2, 4, 6, 8, 12, 16, 24, 32, 48, 64)
+    assert "kCiBuckets[] = {1, 2, 3, 4, 6, 8, 10, 12, 16, 20, 24, 28, kCiMaxNP}" in texts["csrc_cinterp/fir1d_cplx_interp.hip"]
+    assert "kCrBuckets[] = {1, 2, 3, 4, 6, 8, 10, 12, 16, 20, 24, 28, kCrMaxNP}" in texts["csrc_cresample/fir1d_cplx_resample.hip"]
+    assert ci.BUCKETS[:-1] == cr.BUCKETS[:-1] == (1, 2, 3, 4, 6, 8, 10, 12, 16, 20, 24, 28)
+    # the shared exactness tests behind the routes
+    shared = (CSRC.parent / "csrc_cext" / "cext_launch.h").read_text()
+    for line in ("if (acc_bits > 32 || frac > 31) return false;", "if (hq[k] < -32767 || hq[k] > 32767) return false;",
+                 "if (acc_bits < 64) return false;", "return habs * 32768 >= ((unsigned __int128)1 << 63);"):
+        assert line in shared, line
+
+
 # ---- the oracle as the device --------------------------------------------------------------------------
 _RUNS: dict = {}
 
 
 def _oracle_run(c):
-    """(x, y) of a small-scale case, y the oracle's output over the whole of x in the entry's shape."""
+    """(x, y) of a small-scale case, y the oracle's output over the whole of x in the entry's shape
+    (a stream's block behind make_hist's history)."""
     if c.name not in _RUNS:
         x = bic.make_x(c, CPU)
         y = bic.make_y(c, CPU)
         assert bool((y.view(torch.uint8) == bic.SENTINEL).all())
-        ref = bic.reference(c, x.numpy().reshape(c.rows, -1))
+        hist = bic.make_hist(c, CPU).numpy().reshape(c.rows, -1) if c.hist_frames else None
+        assert hist is None or np.array_equal(hist, bic.hist_rows(c, 0, c.rows))
+        ref = bic.reference(c, x.numpy().reshape(c.rows, -1), hist)
         y.copy_(torch.from_numpy(np.ascontiguousarray(ref)).reshape(y.shape))
         _RUNS[c.name] = (x, y)
     return _RUNS[c.name]
+
+
+def _hist_out(c, x):
+    """What a stream's block leaves in hist_out, from the helper's own reference (None: not a stream)."""
+    if not c.hist_frames:
+        return None
+    xs = x.numpy().reshape(c.rows, -1)
+    want = bic.cstream_cases.want_block(xs, bic.hist_rows(c, 0, c.rows), bic.taps_of(c), c.decim, c.phase)[1]
+    return torch.from_numpy(want).reshape((c.rows, -1) if c.rows > 1 else (-1,))
 
 
 def _elems(y):
@@ -130,7 +209,7 @@ def _first_diff(a, b) -> int:
 
 def _rejects(c, x, bad, good, steps):
     with pytest.raises(Mismatch) as e:
-        bic.verify(c, x, bad, chunk=3001)
+        bic.verify(c, x, bad, chunk=3001, hist_out=_hist_out(c, x))
     first = _first_diff(bad, good)
     assert e.value.index == first and e.value.frame == first // c.ch and e.value.step in steps, str(e.value)
     assert f"byte offset {first * c.out_itemsize:#x}" in str(e.value) and f"frame {first // c.ch}" in str(e.value)
@@ -147,7 +226,7 @@ def test_the_oracles_own_output_is_accepted(c):
     else:
         assert torch.equal(x[c.Q:2 * c.Q], x[:c.Q]) and not torch.equal(x[1], x[0])
     for chunk in (bic.CHUNK, 3001, 257):  # one chunk; chunks of several periods; chunks of less than one
-        bic.verify(c, x, y, chunk=chunk)
+        bic.verify(c, x, y, chunk=chunk, hist_out=_hist_out(c, x))
 
 
 ONE_ROW = [c for c in SMALL_TABLE[0::2] if c.rows == 1]  # rows are compared whole
@@ -161,7 +240,8 @@ def test_band_alignment(c):
     for lo, hi in ((0, 1), (1, 40), (n // 3, n // 3 + 257), (n // 2 + 1, n // 2 + 2), (n - 130, n), (n - 1, n), (0, n)):
         a, b, q = bic.input_span(c, lo, hi)
         assert a % c.decim == 0 and 0 <= a < b <= c.width and q * c.decim == a * c.up and q <= lo
-        ref = bic.reference(c, x.reshape(-1)[a * c.ch:b * c.ch].numpy().reshape(1, -1)).reshape(-1)
+        hist = bic.hist_rows(c) if a == 0 else None  # a stream's slice from frame 0 has the history before it
+        ref = bic.reference(c, x.reshape(-1)[a * c.ch:b * c.ch].numpy().reshape(1, -1), hist).reshape(-1)
         got = y.reshape(-1)[lo * c.ch:hi * c.ch].numpy()
         assert np.array_equal(got, ref[(lo - q) * c.ch:(hi - q) * c.ch]), (lo, hi, a, b, q)
 
@@ -170,7 +250,7 @@ def test_band_alignment(c):
 REJECT = [c for c in SMALL_TABLE[0::2] if c.name in (
     "fixed_u8_reg", "fixed_c16_reg", "fixed_i16_long66", "rows_u8_reg_last", "bank4_u8_rows", "ideal_one_row", "ideal_rows",
     "decim_c16_D3_fast", "decim_u8_D2_generic", "interp_u8_U16_fast", "resample_i16_3_2_fast", "resample_u8_2_3_generic",
-    "cplx_5_fast")]
+    "cplx_5_fast", "cdecim_D2_fast", "cinterp_U16_fast", "cresample_3_2_fast", "cstream_D2_fast", "cstream_rows_fast")]
 
 
 @pytest.mark.parametrize("c", REJECT, ids=[c.name for c in REJECT])
@@ -200,7 +280,7 @@ def test_planted_errors_are_rejected_at_the_right_frame(c):
 
     for s in (1, 8, 64):  # one period's worth of outputs (one run of Q rows) computed from x 2^k frames (rows) off
         xs = torch.roll(x.reshape(c.rows, -1), s * (c.ch if one_row else 1), dims=1 if one_row else 0)
-        other = torch.from_numpy(np.ascontiguousarray(bic.reference(c, xs.numpy()))).reshape(good.shape)
+        other = torch.from_numpy(np.ascontiguousarray(bic.reference(c, xs.numpy(), bic.hist_rows(c, 0, c.rows)))).reshape(good.shape)
         bad = good.clone()
         p = 3 * per if one_row else 2 * per
         for f in range(c.filters):
@@ -212,6 +292,21 @@ def test_planted_errors_are_rejected_at_the_right_frame(c):
         bad = good.clone()
         _elems(bad)[at] ^= 1
         _rejects(c, x, bad, good, ("band",))
+
+    if c.hist_frames:  # a stream: one wrong frame in hist_out, in the first row, an inner one and the last
+        right = _hist_out(c, x)
+        He = c.hist_frames * c.ch
+        for at in sorted({3, (c.rows // 2) * He + He // 2, c.rows * He - 1}):
+            wrong = right.clone()
+            wrong.reshape(-1)[at] ^= 1
+            with pytest.raises(Mismatch) as e:
+                bic.verify(c, x, good, chunk=3001, hist_out=wrong)
+            assert (e.value.step, e.value.index, e.value.frame, e.value.count) == ("hist", at, at // c.ch, 1), str(e.value)
+            assert f"hist_out frame {at // c.ch} " in str(e.value) and f"byte offset {at * 2:#x}" in str(e.value)
+        stale = torch.from_numpy(bic.hist_rows(c, 0, c.rows)).reshape(right.shape)  # hist_in copied through
+        with pytest.raises(Mismatch) as e:
+            bic.verify(c, x, good, chunk=3001, hist_out=stale)
+        assert e.value.step == "hist" and e.value.index == _first_diff(stale, right)
 
 
 def test_a_twin_has_nothing_periodic_to_compare_and_is_still_checked():
