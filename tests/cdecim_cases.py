@@ -23,7 +23,7 @@ import cplx_ref
 OUT_U8_SAT, OUT_I32 = 0, 1
 NONE, FAST, GENERIC32, GENERIC64, GENERIC128 = range(5)  # FIR_CDECIM_*
 BUCKETS = (2, 4, 6, 8, 12, 16, 24, 32, 48, 64)
-T, W, MAX_D, MAX_TAPS, ROW_UNIT = 512, 64, 16, 64, 4     # kCdT, kWave, kCdMaxD, kCdMaxTaps, kCdChunk
+T, W, MAX_D, MAX_TAPS, ROW_UNIT = 512, 64, 16, 64, 4     # kTileT, kWave, kTileMaxD, kTileMaxTaps, kChunk
 
 
 def tiles_per_group(D: int) -> int:

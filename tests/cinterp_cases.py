@@ -25,7 +25,7 @@ import cplx_ref
 OUT_U8_SAT, OUT_I32 = 0, 1
 NONE, FAST, GENERIC32, GENERIC64, GENERIC128 = range(5)  # FIR_CINTERP_*
 BUCKETS = (1, 2, 3, 4, 6, 8, 10, 12, 16, 20, 24, 28, 33)
-# kCiF, kBlock, kWave, a lane's frames per pass, kCiMaxU, kCiMaxTaps, kCiMaxPerPhase, kCiChunk
+# kCiF, kBlock, kWave, a lane's frames per pass, kCiMaxU, kCiMaxTaps, kCiMaxPerPhase, kChunk (cext_device.h)
 F, PASS, W, LANE, MAX_U, MAX_TAPS, MAX_PER_PHASE, ROW_UNIT = 2048, 256, 64, 1, 16, 128, 32, 4
 
 

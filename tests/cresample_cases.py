@@ -26,7 +26,7 @@ import cinterp_cases
 OUT_U8_SAT, OUT_I32 = 0, 1
 NONE, FAST, GENERIC32, GENERIC64, GENERIC128 = range(5)  # FIR_CRESAMPLE_*
 BUCKETS = (1, 2, 3, 4, 6, 8, 10, 12, 16, 20, 24, 28, 32)
-# kBlock, kWave, kCrMaxUD, kCrMaxTaps, kCrMaxNP, kCrChunk
+# kBlock, kWave, kCrMaxUD, kCrMaxTaps, kCrMaxNP, kChunk (csrc_cext/cext_device.h)
 PASS, W, MAX_UD, MAX_TAPS, MAX_PER_PHASE, ROW_UNIT = 256, 64, 16, 128, 32, 4
 
 

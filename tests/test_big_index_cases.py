@@ -133,16 +133,17 @@ def test_complex_rate_constants_are_the_sources():
     import cresample_cases as cr
     import cstream_cases as sc
 
-    want = {"csrc_cdecim/fir1d_cplx_decim.hip": {"kCdT": dc.T, "kCdMaxD": dc.MAX_D, "kCdMaxTaps": dc.MAX_TAPS, "kCdChunk": dc.ROW_UNIT},
-            "csrc_cstream/fir1d_cplx_stream.hip": {"kCsT": sc.T, "kCsMaxD": sc.MAX_D, "kCsMaxTaps": sc.MAX_TAPS, "kCsChunk": sc.ROW_UNIT},
+    # the decimating tile kernel of cdecim and cstream and the staging chunk of all four: one definition each
+    want = {"csrc_cext/cext_device.h": {"kTileT": dc.T, "kTileMaxD": dc.MAX_D, "kTileMaxTaps": dc.MAX_TAPS, "kChunk": dc.ROW_UNIT},
             "csrc_cinterp/fir1d_cplx_interp.hip": {"kCiF": ci.F, "kCiMinT": 256, "kCiOutBytes": 16384, "kCiMaxU": ci.MAX_U,
                                                    "kCiMaxTaps": ci.MAX_TAPS, "kCiMaxPerPhase": ci.MAX_PER_PHASE,
-                                                   "kCiMaxNP": ci.BUCKETS[-1], "kCiChunk": ci.ROW_UNIT},
+                                                   "kCiMaxNP": ci.BUCKETS[-1]},
             "csrc_cresample/fir1d_cplx_resample.hip": {"kCrInBytes": 4096, "kCrMinT": 256, "kCrOutBytes": 16384,
                                                        "kCrMaxUD": cr.MAX_UD, "kCrMaxTaps": cr.MAX_TAPS,
-                                                       "kCrMaxNP": cr.MAX_PER_PHASE, "kCrChunk": cr.ROW_UNIT},
+                                                       "kCrMaxNP": cr.MAX_PER_PHASE},
             "csrc/fir_common.h": {"kBlock": ci.PASS, "kWave": dc.W}}
     assert (dc.T, dc.MAX_D, dc.MAX_TAPS, dc.ROW_UNIT, dc.W) == (512, 16, 64, 4, 64) and cr.PASS == ci.PASS == 256
+    assert (sc.T, sc.MAX_D, sc.MAX_TAPS, sc.ROW_UNIT) == (dc.T, dc.MAX_D, dc.MAX_TAPS, dc.ROW_UNIT) and ci.ROW_UNIT == cr.ROW_UNIT == dc.ROW_UNIT
     assert (ci.F, ci.MAX_U, ci.MAX_TAPS, ci.MAX_PER_PHASE, cr.MAX_UD, cr.MAX_TAPS, cr.MAX_PER_PHASE) == (2048, 16, 128, 32, 16, 128, 32)
     texts = {}
     for name, consts in want.items():
@@ -150,16 +151,23 @@ def test_complex_rate_constants_are_the_sources():
         for k, v in consts.items():
             m = re.search(rf"\b{k} = (\d+)\b", text)
             assert m and int(m.group(1)) == v, (name, k, m and m.group(1))
-        if name.startswith("csrc_c"):  # the width limit of every fast route
-            assert "width < ((int64_t)1 << 40)" in text and "rows <= (((int64_t)1 << 31) - 1) / " in text, name
+    # the width limit of every fast route: cdecim and cstream take theirs from the shared predicate
+    texts["csrc_cext/cext_launch.h"] = (CSRC.parent / "csrc_cext" / "cext_launch.h").read_text()
+    for name, limit in (("csrc_cdecim/fir1d_cplx_decim.hip", "csrc_cext/cext_launch.h"), ("csrc_cstream/fir1d_cplx_stream.hip", "csrc_cext/cext_launch.h"),
+                        ("csrc_cinterp/fir1d_cplx_interp.hip", None), ("csrc_cresample/fir1d_cplx_resample.hip", None)):
+        if limit:
+            texts[name] = (CSRC.parent / name).read_text()
+            assert "cext::tile_route_ok(x, rows, width, ow, L, decim, stage, bucket)" in texts[name], name
+        text = texts[limit or name]
+        assert "width < ((int64_t)1 << 40)" in text and "rows <= (((int64_t)1 << 31) - 1) / " in text, name
     # the tap and window buckets
-    for name in ("csrc_cdecim/fir1d_cplx_decim.hip", "csrc_cstream/fir1d_cplx_stream.hip"):
-        assert "{2, 4, 6, 8, 12, 16, 24, 32, 48}" in texts[name] and dc.BUCKETS == sc.BUCKETS == (2, 4, 6, 8, 12, 16, 24, 32, 48, 64)
+    assert "kTileBuckets[] = {2, 4, 6, 8, 12, 16, 24, 32, 48, kTileMaxTaps}" in texts["csrc_cext/cext_device.h"]
+    assert dc.BUCKETS == sc.BUCKETS == (2, 4, 6, 8, 12, 16, 24, 32, 48, 64)
     assert "kCiBuckets[] = {1, 2, 3, 4, 6, 8, 10, 12, 16, 20, 24, 28, kCiMaxNP}" in texts["csrc_cinterp/fir1d_cplx_interp.hip"]
     assert "kCrBuckets[] = {1, 2, 3, 4, 6, 8, 10, 12, 16, 20, 24, 28, kCrMaxNP}" in texts["csrc_cresample/fir1d_cplx_resample.hip"]
     assert ci.BUCKETS[:-1] == cr.BUCKETS[:-1] == (1, 2, 3, 4, 6, 8, 10, 12, 16, 20, 24, 28)
     # the shared exactness tests behind the routes
-    shared = (CSRC.parent / "csrc_cext" / "cext_launch.h").read_text()
+    shared = texts["csrc_cext/cext_launch.h"]
     for line in ("if (acc_bits > 32 || frac > 31) return false;", "if (hq[k] < -32767 || hq[k] > 32767) return false;",
                  "if (acc_bits < 64) return false;", "return habs * 32768 >= ((unsigned __int128)1 << 63);"):
         assert line in shared, line

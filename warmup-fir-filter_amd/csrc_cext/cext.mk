@@ -4,7 +4,7 @@
 #   ID_MACRO  the macro that carries the source id into capi_$(NAME).hip
 # and includes this file; make runs in that directory.  The library goes into ../fir_hip/ so it sits
 # next to its ctypes loader.  It includes the header-only device helpers of ../csrc (fir_common.h,
-# fir_dispatch.h) and the header-only host layer of this directory, compiles nothing from either
+# fir_dispatch.h) and the header-only host and device layers of this directory, compiles nothing from either
 # and links against no other library of the project.
 HIPCC ?= /opt/rocm/bin/hipcc
 ARCH ?= gfx950
@@ -16,7 +16,7 @@ SRCS := $(KERNEL).hip capi_$(NAME).hip
 OBJS := $(patsubst %.hip,build/%.o,$(SRCS))
 # every object depends on all of them: a change to the shared layer rebuilds every library
 HDRS := $(NAME).h ../csrc/fir_common.h ../csrc/fir_dispatch.h ../../include/fir_$(NAME).h ../../include/fir_hip.h \
-	../csrc_cext/cext_capi.h ../csrc_cext/cext_launch.h ../csrc_cext/cext.mk
+	../csrc_cext/cext_capi.h ../csrc_cext/cext_launch.h ../csrc_cext/cext_device.h ../csrc_cext/cext.mk
 # the source id embedded in the library (fir_$(NAME)_build_id); the Python loader checks it
 BUILD_ID := $(shell python3 ../fir_hip/_srcid_ext.py $(NAME))
 

@@ -1,9 +1,10 @@
 // cext_launch.h — the host side that the kernel sources of the complex-tap rate-changing FIRs
 // share (fir1d_cplx_decim.hip, fir1d_cplx_interp.hip, fir1d_cplx_resample.hip,
 // fir1d_cplx_stream.hip): the common head of
-// check(), the exactness tests behind the routes, the generic-32 tap packing, the launch record
-// and the generic kernels' tap-table cache.  No library compiles this directory on its own; each
-// includes this header into its one kernel source.  No device code lives here.
+// check(), the exactness tests behind the routes, the generic-32 tap packing, the launch record,
+// the generic kernels' tap-table cache and launch, and the host half of the decimating tile kernel
+// of cdecim and cstream.  No library compiles this directory on its own; each includes this header
+// into its one kernel source.  The device code they share is in cext_device.h.
 //
 // Everything here has internal linkage (an unnamed namespace, `static`): the libraries are loaded
 // into one process and each keeps its own launch record and table cache.  Nothing `inline` with
@@ -18,7 +19,9 @@
 #include <string>
 #include <vector>
 
+#include "cext_device.h"
 #include "fir_common.h"
+#include "fir_dispatch.h"
 #include "fir_hip.h"
 
 namespace cext {
@@ -140,6 +143,103 @@ static const void* table_locked(const void* host, size_t bytes, hipStream_t s, h
     const uint8_t* hb = (const uint8_t*)host;
     g_tabs.push_back(Table{dev, std::vector<uint8_t>(hb, hb + bytes), d, false});
     return d;
+}
+
+// ---- the launch of a library's generic kernels: k32 its 32-bit kernel (route r32, over the packed
+// table), k64 and k128 the exact ones (r128: the 128-bit sums; over hq itself).  go(kernel, grid,
+// table, t0, t1) launches `kernel` through launch_recorded with the library's own arguments, the
+// device table and the two trailing ints: (shl, frac) of k32, (frac, acc_bits) of the others.
+template <typename K32, typename K64, typename Go>
+static hipError_t launch_generic(int route, int r32, int r128, K32 k32, K64 k64, K64 k128, int64_t n_out,
+                                 const int32_t* hq, int L, int frac, int acc_bits, hipStream_t s, Go go) {
+    const int64_t blocks = (n_out + fir::kBlock - 1) / fir::kBlock;
+    if (blocks >= ((int64_t)1 << 31)) return hipErrorInvalidValue;
+    const dim3 grid((unsigned)blocks);
+    hipError_t e = hipSuccess;
+    std::lock_guard<std::mutex> hold(g_tab_mu);  // until the launch is enqueued
+    if (route == r32) {
+        const std::vector<uint32_t> pk = pack_dot2(hq, L);
+        const void* pd = table_locked(pk.data(), sizeof(uint32_t) * pk.size(), s, &e);
+        return pd ? go(k32, grid, pd, 32 - acc_bits, frac) : e;
+    }
+    const void* td = table_locked(hq, sizeof(int32_t) * 2 * (size_t)L, s, &e);
+    return td ? go(route == r128 ? k128 : k64, grid, td, frac, acc_bits) : e;
+}
+
+// ---- the host half of cext_device.h's decimating tile kernel (cdecim, cstream).
+
+// -1 for a bad decim / phase / width
+static int64_t decim_out_width(int64_t width, int decim, int phase) {
+    if (width < 0 || decim < 1 || phase < 0 || phase >= decim) return -1;
+    return width > phase ? (width - phase - 1) / decim + 1 : 0;  // ceil without overflow near 2^63
+}
+
+static int tile_bucket_of(int L) {
+    for (const int b : kTileBuckets)
+        if (L <= b) return b;
+    return kTileMaxTaps;
+}
+
+// The geometry a call needs for the tile kernel (the exactness test, dot2_ok, is the caller's).
+// Sets the tap bucket when it holds.
+static bool tile_route_ok(uintptr_t x, int64_t rows, int64_t width, int64_t ow, int L, int decim, int stage, int* bucket) {
+    if (decim < 2 || decim > kTileMaxD || L > kTileMaxTaps || stage != FIR_OUT_I32 || x % 16 != 0 ||
+        (rows != 1 && width % kChunk != 0))  // every row starts as x does
+        return false;
+    const int64_t tiles = (ow + kTileT - 1) / kTileT;
+    // the grid is at most rows * tiles < 2^31 workgroups; the kernel holds a tile index in 32 bits
+    if (!(width < ((int64_t)1 << 40) && rows <= (((int64_t)1 << 31) - 1) / tiles)) return false;
+    *bucket = tile_bucket_of(L);
+    return true;
+}
+
+// go(IntTag<LP>) for the bucket LP
+template <typename Go>
+static hipError_t with_tile_bucket(int bucket, Go go) {
+    switch (bucket) {
+        case 2: return go(fir::IntTag<2>{});
+        case 4: return go(fir::IntTag<4>{});
+        case 6: return go(fir::IntTag<6>{});
+        case 8: return go(fir::IntTag<8>{});
+        case 12: return go(fir::IntTag<12>{});
+        case 16: return go(fir::IntTag<16>{});
+        case 24: return go(fir::IntTag<24>{});
+        case 32: return go(fir::IntTag<32>{});
+        case 48: return go(fir::IntTag<48>{});
+        default: return go(fir::IntTag<kTileMaxTaps>{});
+    }
+}
+
+// the taps in window order, zero-padded to LP
+template <int LP>
+static TileTaps<LP> pack_window_taps(const int32_t* hq, int L) {
+    TileTaps<LP> t;
+    for (int p = 0; p < LP; ++p) {
+        const int32_t hr = p < L ? hq[2 * (L - 1 - p)] : 0, hi = p < L ? hq[2 * (L - 1 - p) + 1] : 0;
+        const uint32_t r16 = (uint32_t)hr & 0xFFFFu, i16 = (uint32_t)hi & 0xFFFFu, ni16 = (uint32_t)(-hi) & 0xFFFFu;
+        t.a[p] = r16 | (ni16 << 16);
+        t.b[p] = i16 | (r16 << 16);
+    }
+    return t;
+}
+
+// the launch geometry of bucket LP at decimation D
+struct TileGeom {
+    int G, PL;  // tiles per workgroup, dwords per plane
+    uint32_t magic, groups;
+    size_t lds;
+    dim3 grid;
+};
+static TileGeom tile_geom(int D, int LP, int64_t rows, int64_t ow) {
+    TileGeom g;
+    g.G = tile_tiles_per_group(D);
+    g.PL = (tile_chunks(kChunk - 1, g.G, D, LP) * kChunk + D - 1) / D;
+    g.magic = (1u << kMagicShift) / (uint32_t)D + 1;
+    const int64_t groups = (ow + (int64_t)g.G * kTileT - 1) / ((int64_t)g.G * kTileT);
+    g.groups = (uint32_t)groups;
+    g.lds = (size_t)D * g.PL * sizeof(uint32_t);
+    g.grid = dim3((unsigned)(rows * groups));
+    return g;
 }
 
 }  // namespace

@@ -9,9 +9,9 @@
 //
 // The arithmetic is csrc/fir1d_cplx.hip's (frames outside a row are zero, one exact sum per part,
 // wrapped once, overflow-free round-half-up, int32 or saturated-u8 stage), the tiling and the LDS
-// output stage csrc/fir1d_interp.hip's.  This file is the whole device side of libfir_cinterp.so; it
-// shares the header-only device helpers of csrc/ (fir_common.h, fir_dispatch.h) and nothing compiled
-// from it or from csrc_cdecim/.
+// output stage csrc/fir1d_interp.hip's.  This file is libfir_cinterp.so's own device side; it shares
+// the header-only device helpers of csrc/ (fir_common.h, fir_dispatch.h) and of csrc_cext/
+// (cext_device.h: the output-run writer, the generic kernels' steps) and nothing compiled from either.
 //
 //  * fir1d_cplx_interp_kernel — the hot path (FIR_CINTERP_FAST, see route_of).  One interleaved frame
 //    is one dword, and v_dot2_i32_i16 of it against A = (hr, -hi) is the real part of one tap's
@@ -63,10 +63,7 @@
 //    cached device table.  fir1d_cplx_interp_generic32_kernel (int16-sized parts, acc_bits <= 32,
 //    frac <= 31, x 4-byte aligned): 32-bit wrap-around sums, two v_dot2 per tap over a packed (A, B)
 //    table.  fir1d_cplx_interp_generic_kernel: exact 64-bit sums, or 128-bit when needs_wide says so.
-#include <mutex>
 #include <string>
-#include <type_traits>
-#include <vector>
 
 #include "cinterp.h"
 #include "cext_launch.h"
@@ -75,10 +72,8 @@
 
 namespace cinterp {
 
-using cext::dot2_ok;
+using cext::kChunk;  // frames per staging step of one thread (16 bytes)
 using cext::launch_recorded;
-using cext::needs_wide;
-using cext::table_locked;
 using fir::dot2_acc;
 using fir::IntTag;
 using fir::kBlock;
@@ -91,13 +86,12 @@ constexpr int kCiMaxU = 16;
 constexpr int kCiMaxTaps = 128;
 constexpr int kCiMaxPerPhase = 32;  // ceil(L / U) of the fast path
 constexpr int kCiMaxNP = 33;        // the largest window bucket: ceil(L / U) + 1
-constexpr int kCiChunk = 4;         // frames per staging step of one thread (16 bytes)
 
 // 16-byte chunks a workgroup stages: lead + its frames + the last frame's window (NP - 1 more)
 __host__ __device__ constexpr int ci_chunks(int lead, int frames, int NP) {
-    return (lead + frames + NP - 1 + kCiChunk - 1) / kCiChunk;
+    return (lead + frames + NP - 1 + kChunk - 1) / kChunk;
 }
-constexpr int kCiMaxIt = (ci_chunks(kCiChunk - 1, kCiF, kCiMaxNP) + kBlock - 1) / kBlock;  // staging steps per thread
+constexpr int kCiMaxIt = (ci_chunks(kChunk - 1, kCiF, kCiMaxNP) + kBlock - 1) / kBlock;  // staging steps per thread
 static_assert(kCiMaxIt == 3, "staging steps");
 
 // the window buckets, and the one below a bucket (0 below the first)
@@ -120,11 +114,6 @@ constexpr int ci_slots(int NP) {
 }
 static_assert(ci_slots(1) == 16 && ci_slots(16) == 176 && ci_slots(kCiMaxNP) == 132, "tap table sizes");
 
-// the output stage: logical byte b at b + 4 * (b / 128)
-__host__ __device__ constexpr uint32_t ci_phys(uint32_t b) { return b + ((b >> 7) << 2); }
-
-typedef uint32_t ci_u4 __attribute__((ext_vector_type(4)));
-
 template <int NP>
 struct TapsCi {
     uint32_t a[ci_slots(NP)];  // phase e, window dword w at e * NP + w: (hr, -hi) of the tap that meets it
@@ -144,21 +133,22 @@ __global__ __launch_bounds__(kBlock) void fir1d_cplx_interp_kernel(const uint32_
     const int nf = left < kCiF ? (int)left : kCiF;  // its frames (the row's last workgroup: fewer)
     const int gt = (nf + T - 1) / T;                // its tiles
     const int64_t a0 = i0 + S;                      // its first window's first frame (may be < 0)
-    const int64_t o = a0 & ~(int64_t)(kCiChunk - 1);  // LDS origin: floor to 4 frames
+    const int64_t o = a0 & ~(int64_t)(kChunk - 1);  // LDS origin: floor to 4 frames
     const int lead = (int)(a0 - o);                 // 0..3
     const int nchunks = ci_chunks(lead, nf, NP);
     const uint32_t* __restrict__ xr = x + r * width;
 
     // ---- stage frames [o, o + 4 * nchunks) of the row (zero outside [0, width)): first every load
-    // of the thread, then the LDS writes
-    ci_u4 raw[kCiMaxIt];
+    // of the thread, then the LDS writes.  The load loop is cext::stage_load's, kept as this
+    // kernel's own text: through the helper hipcc allots the small buckets two VGPRs fewer.
+    cext::u4 raw[kCiMaxIt];
 #pragma unroll
     for (int it = 0; it < kCiMaxIt; ++it) {
         const int k = threadIdx.x + it * kBlock;
         if (k >= nchunks) break;
-        const int64_t f = o + (int64_t)k * kCiChunk;
-        if (f >= 0 && f + kCiChunk <= width) {
-            raw[it] = *reinterpret_cast<const ci_u4*>(xr + f);
+        const int64_t f = o + (int64_t)k * kChunk;
+        if (f >= 0 && f + kChunk <= width) {
+            raw[it] = *reinterpret_cast<const cext::u4*>(xr + f);
         } else {  // a chunk that crosses a row end, or lies outside the row
             raw[it].x = f >= 0 && f < width ? xr[f] : 0u;
             raw[it].y = f + 1 >= 0 && f + 1 < width ? xr[f + 1] : 0u;
@@ -170,7 +160,7 @@ __global__ __launch_bounds__(kBlock) void fir1d_cplx_interp_kernel(const uint32_
     for (int it = 0; it < kCiMaxIt; ++it) {
         const int k = threadIdx.x + it * kBlock;
         if (k >= nchunks) break;
-        *reinterpret_cast<ci_u4*>(ci_lds + kCiChunk * k) = raw[it];
+        *reinterpret_cast<cext::u4*>(ci_lds + kChunk * k) = raw[it];
     }
     __syncthreads();
 
@@ -207,29 +197,14 @@ __global__ __launch_bounds__(kBlock) void fir1d_cplx_interp_kernel(const uint32_
                         im = dot2_acc(d[w], tq[w], im);
                     }
                 }
-                outw[ci_phys(b) >> 2] = (uint32_t)fir::round_acc<ACC32>(re, shl, frac);
-                outw[ci_phys(b + 4u) >> 2] = (uint32_t)fir::round_acc<ACC32>(im, shl, frac);
+                outw[cext::phys(b) >> 2] = (uint32_t)fir::round_acc<ACC32>(re, shl, frac);
+                outw[cext::phys(b + 4u) >> 2] = (uint32_t)fir::round_acc<ACC32>(im, shl, frac);
             }
         }
         __syncthreads();
 
         // ---- the tile's output run [sh, end) of the stage, as 16-byte vectors at 16-byte addresses
-        const uint32_t end = sh + (uint32_t)nv * fstep;
-        const uint32_t nvec = (end + 15u) >> 4;
-        for (uint32_t v = threadIdx.x; v < nvec; v += kBlock) {
-            const uint32_t lo = 16u * v;
-            if (lo >= sh && lo + 16u <= end) {
-                ci_u4 q;
-                q.x = outw[ci_phys(lo) >> 2];
-                q.y = outw[ci_phys(lo + 4) >> 2];
-                q.z = outw[ci_phys(lo + 8) >> 2];
-                q.w = outw[ci_phys(lo + 12) >> 2];
-                *reinterpret_cast<ci_u4*>(yt - sh + lo) = q;
-            } else {  // the partial vector at either end of the run
-                const uint32_t b0 = lo < sh ? sh : lo, b1 = lo + 16u < end ? lo + 16u : end;
-                for (uint32_t b = b0; b < b1; b += 4u) *reinterpret_cast<uint32_t*>(yt - sh + b) = outw[ci_phys(b) >> 2];
-            }
-        }
+        cext::write_run(outw, yt, sh, sh + (uint32_t)nv * fstep);
         __syncthreads();  // the next tile overwrites the stage
     }
 }
@@ -246,35 +221,14 @@ __global__ __launch_bounds__(kBlock) void fir1d_cplx_interp_generic_kernel(const
     if (gi >= n_out) return;
     const int64_t out_width = width * U;
     const int64_t j = gi % out_width, r = gi / out_width;
-    const int64_t i = j / U, e = j % U;
-    const int64_t pe = (e + L / 2) % U, n = i + (e + L / 2) / U;  // tap pe + U * t reads frame n - t
-    // 0 <= n - t < width  <=>  n - width < t <= n;  pe + U * t <= L - 1
-    const int64_t t_lo = n - width + 1 > 0 ? n - width + 1 : 0;
-    const int64_t t_max = pe < L ? (L - 1 - pe) / U : -1;
-    const int64_t t_hi = n < t_max ? n : t_max;
+    const cext::PolyWalk w = cext::poly_walk(j, U, L, width);
     const int16_t* __restrict__ xr = x + 2 * r * width;
-    using Acc = typename std::conditional<WIDE, unsigned __int128, uint64_t>::type;
-    using SAcc = typename std::conditional<WIDE, __int128, int64_t>::type;
-    Acc re = 0, im = 0;
-    for (int64_t t = t_lo; t <= t_hi; ++t) {
-        const int64_t k = pe + U * t;
-        const int64_t hr = taps[2 * k], hi = taps[2 * k + 1];
-        const int64_t f = n - t;
-        const int64_t ar = xr[2 * f], ai = xr[2 * f + 1];
-        re += (Acc)(SAcc)(hr * ar) - (Acc)(SAcc)(hi * ai);
-        im += (Acc)(SAcc)(hr * ai) + (Acc)(SAcc)(hi * ar);
-    }
-    if constexpr (WIDE) {
-        y[2 * gi] = fir::stage_out128<STAGE>(fir::round128((__int128)re, frac, acc_bits));
-        y[2 * gi + 1] = fir::stage_out128<STAGE>(fir::round128((__int128)im, frac, acc_bits));
-    } else {
-        y[2 * gi] = fir::stage_out<STAGE>(fir::round64((int64_t)re, frac, acc_bits));
-        y[2 * gi + 1] = fir::stage_out<STAGE>(fir::round64((int64_t)im, frac, acc_bits));
-    }
+    cext::Acc<WIDE> re = 0, im = 0;
+    for (int64_t t = w.t_lo; t <= w.t_hi; ++t) cext::cmac<WIDE>(re, im, taps, w.pe + U * t, xr, w.n - t);
+    cext::store_frame<STAGE, WIDE>(y, gi, re, im, frac, acc_bits);
 }
 
-// The same walk on 32-bit wrap-around accumulators: pk[2k] = (hr[k], -hi[k]), pk[2k + 1] =
-// (hi[k], hr[k]), two v_dot2_i32_i16 per tap; a frame is one aligned dword.
+// The same walk on 32-bit wrap-around accumulators over the packed table; a frame is one aligned dword.
 template <int STAGE>
 __global__ __launch_bounds__(kBlock) void fir1d_cplx_interp_generic32_kernel(
     const uint32_t* __restrict__ x, typename OutTraits<STAGE>::T* __restrict__ y, int64_t n_out, int64_t width, int64_t U,
@@ -283,21 +237,11 @@ __global__ __launch_bounds__(kBlock) void fir1d_cplx_interp_generic32_kernel(
     if (gi >= n_out) return;
     const int64_t out_width = width * U;
     const int64_t j = gi % out_width, r = gi / out_width;
-    const int64_t i = j / U, e = j % U;
-    const int64_t pe = (e + L / 2) % U, n = i + (e + L / 2) / U;
-    const int64_t t_lo = n - width + 1 > 0 ? n - width + 1 : 0;
-    const int64_t t_max = pe < L ? (L - 1 - pe) / U : -1;
-    const int64_t t_hi = n < t_max ? n : t_max;
-    const uint32_t* __restrict__ xf = x + r * width + n;  // tap pe + U * t meets frame xf[-t]
+    const cext::PolyWalk w = cext::poly_walk(j, U, L, width);
+    const uint32_t* __restrict__ xf = x + r * width + w.n;  // tap pe + U * t meets frame xf[-t]
     uint32_t re = 0, im = 0;
-    for (int64_t t = t_lo; t <= t_hi; ++t) {
-        const uint32_t d = xf[-t];
-        const int64_t k = pe + U * t;
-        re = dot2_acc(d, pk[2 * k], re);
-        im = dot2_acc(d, pk[2 * k + 1], im);
-    }
-    y[2 * gi] = fir::stage_out32<STAGE>(fir::round32(re, shl, frac));
-    y[2 * gi + 1] = fir::stage_out32<STAGE>(fir::round32(im, shl, frac));
+    for (int64_t t = w.t_lo; t <= w.t_hi; ++t) cext::cmac32(re, im, pk, w.pe + U * t, xf[-t]);
+    cext::store_frame32<STAGE>(y, gi, re, im, shl, frac);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -356,9 +300,9 @@ int route_of(uintptr_t x, uintptr_t y, int64_t rows, int64_t width, const int32_
              int acc_bits, int stage, int* bucket) {
     (void)y;  // y may sit at any element address on every route
     *bucket = 0;
-    const bool d2 = dot2_ok(hq, L, frac, acc_bits);
+    const bool d2 = cext::dot2_ok(hq, L, frac, acc_bits);
     if (d2 && up >= 2 && up <= kCiMaxU && L <= kCiMaxTaps && (L + up - 1) / up <= kCiMaxPerPhase &&
-        stage == FIR_OUT_I32 && x % 16 == 0 && (rows == 1 || width % kCiChunk == 0)) {  // every row starts as x does
+        stage == FIR_OUT_I32 && x % 16 == 0 && (rows == 1 || width % kChunk == 0)) {  // every row starts as x does
         const int64_t groups = (width + kCiF - 1) / kCiF;
         // the grid is rows * groups < 2^31 workgroups; the kernel holds a group index in 32 bits
         if (width < ((int64_t)1 << 40) && rows <= (((int64_t)1 << 31) - 1) / groups) {
@@ -368,7 +312,7 @@ int route_of(uintptr_t x, uintptr_t y, int64_t rows, int64_t width, const int32_
         }
     }
     if (d2 && x % 4 == 0) return FIR_CINTERP_GENERIC32;
-    return needs_wide(hq, L, acc_bits) ? FIR_CINTERP_GENERIC128 : FIR_CINTERP_GENERIC64;
+    return cext::needs_wide(hq, L, acc_bits) ? FIR_CINTERP_GENERIC128 : FIR_CINTERP_GENERIC64;
 }
 
 // what the calling thread's last launch() launched: every kernel goes through cext::launch_recorded
@@ -392,9 +336,9 @@ static hipError_t launch_fast_np(const void* x, void* y, int64_t rows, int64_t w
         }
     }
     const int T = tile_of(U);
-    const int PL = ci_chunks(kCiChunk - 1, kCiF, NP) * kCiChunk;  // window dwords (lead <= 3)
+    const int PL = ci_chunks(kChunk - 1, kCiF, NP) * kChunk;  // window dwords (lead <= 3)
     const uint32_t stage_bytes = (uint32_t)(T * U * 8) + 16u;
-    const size_t lds = (size_t)PL * sizeof(uint32_t) + ci_phys(stage_bytes) + 4;
+    const size_t lds = (size_t)PL * sizeof(uint32_t) + cext::phys(stage_bytes) + 4;
     const int64_t groups = (width + kCiF - 1) / kCiF;
     const dim3 grid((unsigned)(rows * groups));
     if (acc_bits == 32)
@@ -428,32 +372,6 @@ static hipError_t launch_fast(int bucket, const void* x, void* y, int64_t rows, 
     }
 }
 
-template <int STAGE>
-static hipError_t launch_generic(int route, const void* x, void* y, int64_t rows, int64_t width, const int32_t* hq, int L,
-                                 int U, int frac, int acc_bits, hipStream_t s) {
-    using OutT = typename OutTraits<STAGE>::T;
-    const int64_t n_out = rows * width * U;
-    const int64_t blocks = (n_out + kBlock - 1) / kBlock;
-    if (blocks >= ((int64_t)1 << 31)) return hipErrorInvalidValue;
-    const dim3 grid((unsigned)blocks);
-    hipError_t e = hipSuccess;
-    std::lock_guard<std::mutex> hold(cext::g_tab_mu);  // until the launch is enqueued
-    if (route == FIR_CINTERP_GENERIC32) {
-        const std::vector<uint32_t> pk = cext::pack_dot2(hq, L);
-        const uint32_t* pd = (const uint32_t*)table_locked(pk.data(), sizeof(uint32_t) * pk.size(), s, &e);
-        if (!pd) return e;
-        return launch_recorded(route, 0, fir1d_cplx_interp_generic32_kernel<STAGE>, grid, 0, s, (const uint32_t*)x,
-                               (OutT*)y, n_out, width, (int64_t)U, pd, L, 32 - acc_bits, frac);
-    }
-    const int32_t* td = (const int32_t*)table_locked(hq, sizeof(int32_t) * 2 * (size_t)L, s, &e);
-    if (!td) return e;
-    if (route == FIR_CINTERP_GENERIC128)
-        return launch_recorded(route, 0, fir1d_cplx_interp_generic_kernel<STAGE, true>, grid, 0, s, (const int16_t*)x,
-                               (OutT*)y, n_out, width, (int64_t)U, td, L, frac, acc_bits);
-    return launch_recorded(route, 0, fir1d_cplx_interp_generic_kernel<STAGE, false>, grid, 0, s, (const int16_t*)x,
-                           (OutT*)y, n_out, width, (int64_t)U, td, L, frac, acc_bits);
-}
-
 int launch(const int16_t* x, int64_t rows, int64_t width, const int32_t* hq, int L, int up, int frac, int acc_bits,
            int stage, void* y, hipStream_t stream, std::string* err) {
     const int rc = check(x, y, rows, width, hq, L, up, frac, acc_bits, stage, err);
@@ -467,7 +385,13 @@ int launch(const int16_t* x, int64_t rows, int64_t width, const int32_t* hq, int
         e = launch_fast(bucket, x, y, rows, width, hq, L, up, frac, acc_bits, stream);
     else
         e = fir::with_stage(stage, [&](auto st) {
-            return launch_generic<st>(route, x, y, rows, width, hq, L, up, frac, acc_bits, stream);
+            return cext::launch_generic(
+                route, FIR_CINTERP_GENERIC32, FIR_CINTERP_GENERIC128, fir1d_cplx_interp_generic32_kernel<st>,
+                fir1d_cplx_interp_generic_kernel<st, false>, fir1d_cplx_interp_generic_kernel<st, true>, rows * width * up,
+                hq, L, frac, acc_bits, stream, [&](auto kernel, dim3 grid, const void* table, int t0, int t1) {
+                    return launch_recorded(route, 0, kernel, grid, 0, stream, x, y, rows * width * up, width, (int64_t)up,
+                                           table, L, t0, t1);
+                });
         });
     if (e != hipSuccess) return *err = std::string("fir1d cplx interp launch failed: ") + hipGetErrorString(e), FIR_EHIP;
     return FIR_OK;

@@ -12,9 +12,9 @@
 // p_q and c_q depend on q alone and the pattern repeats every U output frames = D input frames (one
 // PERIOD v).  The arithmetic is csrc/fir1d_cplx.hip's (frames outside a row are zero, one exact sum
 // per part, wrapped once, overflow-free round-half-up, int32 or saturated-u8 stage).  This file is
-// the whole device side of libfir_cresample.so; it shares the header-only device helpers of csrc/
-// (fir_common.h, fir_dispatch.h) and nothing compiled from it, from csrc_cdecim/ or from
-// csrc_cinterp/.
+// libfir_cresample.so's own device side; it shares the header-only device helpers of csrc/
+// (fir_common.h, fir_dispatch.h) and of csrc_cext/ (cext_device.h: input staging, the plane
+// scatter, the output-run writer, the generic kernels' steps) and nothing compiled from either.
 //
 //  * fir1d_cplx_resample_kernel — the hot path (FIR_CRESAMPLE_FAST, see route_of): the decimator's
 //    input side, the interpolator's output side and the complex MAC.  One interleaved frame is one
@@ -62,10 +62,7 @@
 //    fir1d_cplx_resample_generic32_kernel (int16-sized parts, acc_bits <= 32, frac <= 31, x 4-byte
 //    aligned): 32-bit wrap-around sums, two v_dot2 per tap over a packed (A, B) table.
 //    fir1d_cplx_resample_generic_kernel: exact 64-bit sums, or 128-bit when needs_wide says so.
-#include <mutex>
 #include <string>
-#include <type_traits>
-#include <vector>
 
 #include "cresample.h"
 #include "cext_launch.h"
@@ -74,10 +71,8 @@
 
 namespace cresample {
 
-using cext::dot2_ok;
+using cext::kChunk;  // frames per staging step of one thread (16 bytes)
 using cext::launch_recorded;
-using cext::needs_wide;
-using cext::table_locked;
 using fir::dot2_acc;
 using fir::IntTag;
 using fir::kBlock;
@@ -89,10 +84,7 @@ constexpr int kCrOutBytes = 16384;  // T = P halved while T * U * 8 exceeds this
 constexpr int kCrMaxUD = 16;        // 2 <= U, D <= 16
 constexpr int kCrMaxTaps = 128;
 constexpr int kCrMaxNP = 32;        // the largest tap bucket: ceil(L / U) of the fast path
-constexpr int kCrChunk = 4;         // frames per staging step of one thread (16 bytes)
 constexpr int kCrOffs = 64;         // window dwords a lane can address: the highest k0 + NP is 17 + 32
-// a / D == (a * (2^18 / D + 1)) >> 18 for a < 2^14 and 2 <= D <= 16 (as the decimator's)
-constexpr int kCrMagicShift = 18;
 
 // periods per workgroup
 __host__ __device__ constexpr int cr_periods(int D) {
@@ -103,20 +95,20 @@ __host__ __device__ constexpr int cr_periods(int D) {
 // 16-byte chunks a workgroup of n periods stages: lead + the last period's first frame + ext, the
 // frames from there to the end of the furthest window (the highest k0 + NP)
 __host__ __device__ constexpr int cr_chunks(int lead, int n, int D, int ext) {
-    return (lead + (n - 1) * D + ext + kCrChunk - 1) / kCrChunk;
+    return (lead + (n - 1) * D + ext + kChunk - 1) / kChunk;
 }
 constexpr int kCrMaxExt = kCrMaxUD + 1 + kCrMaxNP;  // k0 <= D + 1
 constexpr int cr_max_chunks() {
     int m = 0;
     for (int D = 2; D <= kCrMaxUD; ++D) {
-        const int c = cr_chunks(kCrChunk - 1, cr_periods(D), D, kCrMaxExt);
+        const int c = cr_chunks(kChunk - 1, cr_periods(D), D, kCrMaxExt);
         m = c > m ? c : m;
     }
     return m;
 }
 constexpr int kCrMaxIt = (cr_max_chunks() + kBlock - 1) / kBlock;  // staging steps per thread
 static_assert(kCrMaxIt == 5, "staging steps");
-static_assert(kCrChunk * kCrMaxIt * kBlock < (1 << 14), "the magic division's range");
+static_assert(kChunk * kCrMaxIt * kBlock < (1 << 14), "the magic division's range");
 static_assert(kCrMaxExt <= kCrOffs, "the offset table holds every window dword");
 
 // the tap buckets, and the one below a bucket (0 below the first)
@@ -138,11 +130,6 @@ constexpr int cr_slots(int NP) {
     return umax * NP;
 }
 static_assert(cr_slots(1) == 16 && cr_slots(16) == 160 && cr_slots(kCrMaxNP) == 128, "tap table sizes");
-
-// the output stage: logical byte b at b + 4 * (b / 128)
-__host__ __device__ constexpr uint32_t cr_phys(uint32_t b) { return b + ((b >> 7) << 2); }
-
-typedef uint32_t cr_u4 __attribute__((ext_vector_type(4)));
 
 template <int NP>
 struct TapsCr {
@@ -167,45 +154,16 @@ __global__ __launch_bounds__(kBlock) void fir1d_cplx_resample_kernel(const uint3
     const int64_t left = (out_width - m0 + TU - 1) / TU;
     const int gt = left < P / T ? (int)left : P / T;  // its tiles (the row's last workgroup: fewer)
     const int64_t a0 = v0 * D + S;                    // its first window's first frame (may be < 0)
-    const int64_t o = a0 & ~(int64_t)(kCrChunk - 1);  // the first frame staged: floor to 4 frames
+    const int64_t o = a0 & ~(int64_t)(kChunk - 1);    // the first frame staged: floor to 4 frames
     const int lead = (int)(a0 - o);                   // 0..3
     const int nchunks = cr_chunks(lead, gt * T, D, ext);
     const uint32_t* __restrict__ xr = x + r * width;
 
-    // ---- stage frames [o, o + 4 * nchunks) of the row (zero outside [0, width)): first every load
-    // of the thread, then the LDS writes
-    uint32_t raw[kCrMaxIt][kCrChunk];
-#pragma unroll
-    for (int it = 0; it < kCrMaxIt; ++it) {
-        const int k = threadIdx.x + it * kBlock;
-        if (k >= nchunks) break;
-        const int64_t f = o + (int64_t)k * kCrChunk;
-        if (f >= 0 && f + kCrChunk <= width) {
-            const cr_u4 q = *reinterpret_cast<const cr_u4*>(xr + f);
-            raw[it][0] = q.x;
-            raw[it][1] = q.y;
-            raw[it][2] = q.z;
-            raw[it][3] = q.w;
-        } else {  // a chunk that crosses a row end, or lies outside the row
-#pragma unroll
-            for (int j = 0; j < kCrChunk; ++j) raw[it][j] = f + j >= 0 && f + j < width ? xr[f + j] : 0u;
-        }
-    }
-#pragma unroll
-    for (int it = 0; it < kCrMaxIt; ++it) {
-        const int k = threadIdx.x + it * kBlock;
-        if (k >= nchunks) break;
-#pragma unroll
-        for (int i = 0; i < kCrChunk; ++i) {
-            const int ai = kCrChunk * k + i - lead;  // LDS dword 0 is the first window's first frame a0
-            if (ai < 0) continue;                    // the up to 3 frames in front of it are never read
-            const uint32_t a = (uint32_t)ai;
-            // every factor is below 2^24: v_mul_u32_u24 (full rate) instead of v_mul_lo_u32
-            const uint32_t idx = (uint32_t)__umul24(a, magic) >> kCrMagicShift;  // a / D
-            const uint32_t pl = a - (uint32_t)__umul24(idx, (uint32_t)D);        // a % D
-            cr_lds[(uint32_t)__umul24(pl, (uint32_t)PL) + idx] = raw[it][i];
-        }
-    }
+    // ---- stage frames [o, o + 4 * nchunks) of the row (zero outside [0, width)) in D planes; LDS
+    // dword 0 is the first window's first frame a0 (the up to 3 frames in front of it are never read)
+    cext::u4 raw[kCrMaxIt];
+    cext::stage_load(raw, xr, o, nchunks, width, [&](int64_t f) { return f >= 0 && f < width ? xr[f] : 0u; });
+    cext::scatter_planes(cr_lds, raw, nchunks, lead, D, PL, magic);
     __syncthreads();
 
     uint32_t* const outw = cr_lds + ((D * PL + 3) & ~3);
@@ -240,29 +198,14 @@ __global__ __launch_bounds__(kBlock) void fir1d_cplx_resample_kernel(const uint3
                         im = dot2_acc(d[w - c * CW], tq[w], im);
                     }
                 }
-                outw[cr_phys(b) >> 2] = (uint32_t)fir::round_acc<ACC32>(re, shl, frac);
-                outw[cr_phys(b + 4u) >> 2] = (uint32_t)fir::round_acc<ACC32>(im, shl, frac);
+                outw[cext::phys(b) >> 2] = (uint32_t)fir::round_acc<ACC32>(re, shl, frac);
+                outw[cext::phys(b + 4u) >> 2] = (uint32_t)fir::round_acc<ACC32>(im, shl, frac);
             }
         }
         __syncthreads();
 
         // ---- the tile's output run [sh, end) of the stage, as 16-byte vectors at 16-byte addresses
-        const uint32_t end = sh + (uint32_t)no * 8u;
-        const uint32_t nvec = (end + 15u) >> 4;
-        for (uint32_t v = threadIdx.x; v < nvec; v += kBlock) {
-            const uint32_t lo = 16u * v;
-            if (lo >= sh && lo + 16u <= end) {
-                cr_u4 q;
-                q.x = outw[cr_phys(lo) >> 2];
-                q.y = outw[cr_phys(lo + 4) >> 2];
-                q.z = outw[cr_phys(lo + 8) >> 2];
-                q.w = outw[cr_phys(lo + 12) >> 2];
-                *reinterpret_cast<cr_u4*>(yt - sh + lo) = q;
-            } else {  // the partial vector at either end of the run
-                const uint32_t b0 = lo < sh ? sh : lo, b1 = lo + 16u < end ? lo + 16u : end;
-                for (uint32_t b = b0; b < b1; b += 4u) *reinterpret_cast<uint32_t*>(yt - sh + b) = outw[cr_phys(b) >> 2];
-            }
-        }
+        cext::write_run(outw, yt, sh, sh + (uint32_t)no * 8u);
         __syncthreads();  // the next tile overwrites the stage
     }
 }
@@ -279,35 +222,14 @@ __global__ __launch_bounds__(kBlock) void fir1d_cplx_resample_generic_kernel(
     if (gi >= n_out) return;
     const int64_t m = gi % out_width, r = gi / out_width;
     const int64_t j = m * D + phase;  // < width * U
-    const int64_t i = j / U, e = j % U;
-    const int64_t pe = (e + L / 2) % U, n = i + (e + L / 2) / U;  // tap pe + U * t reads frame n - t
-    // 0 <= n - t < width  <=>  n - width < t <= n;  pe + U * t <= L - 1
-    const int64_t t_lo = n - width + 1 > 0 ? n - width + 1 : 0;
-    const int64_t t_max = pe < L ? (L - 1 - pe) / U : -1;
-    const int64_t t_hi = n < t_max ? n : t_max;
+    const cext::PolyWalk w = cext::poly_walk(j, U, L, width);
     const int16_t* __restrict__ xr = x + 2 * r * width;
-    using Acc = typename std::conditional<WIDE, unsigned __int128, uint64_t>::type;
-    using SAcc = typename std::conditional<WIDE, __int128, int64_t>::type;
-    Acc re = 0, im = 0;
-    for (int64_t t = t_lo; t <= t_hi; ++t) {
-        const int64_t k = pe + U * t;
-        const int64_t hr = taps[2 * k], hi = taps[2 * k + 1];
-        const int64_t f = n - t;
-        const int64_t ar = xr[2 * f], ai = xr[2 * f + 1];
-        re += (Acc)(SAcc)(hr * ar) - (Acc)(SAcc)(hi * ai);
-        im += (Acc)(SAcc)(hr * ai) + (Acc)(SAcc)(hi * ar);
-    }
-    if constexpr (WIDE) {
-        y[2 * gi] = fir::stage_out128<STAGE>(fir::round128((__int128)re, frac, acc_bits));
-        y[2 * gi + 1] = fir::stage_out128<STAGE>(fir::round128((__int128)im, frac, acc_bits));
-    } else {
-        y[2 * gi] = fir::stage_out<STAGE>(fir::round64((int64_t)re, frac, acc_bits));
-        y[2 * gi + 1] = fir::stage_out<STAGE>(fir::round64((int64_t)im, frac, acc_bits));
-    }
+    cext::Acc<WIDE> re = 0, im = 0;
+    for (int64_t t = w.t_lo; t <= w.t_hi; ++t) cext::cmac<WIDE>(re, im, taps, w.pe + U * t, xr, w.n - t);
+    cext::store_frame<STAGE, WIDE>(y, gi, re, im, frac, acc_bits);
 }
 
-// The same walk on 32-bit wrap-around accumulators: pk[2k] = (hr[k], -hi[k]), pk[2k + 1] =
-// (hi[k], hr[k]), two v_dot2_i32_i16 per tap; a frame is one aligned dword.
+// The same walk on 32-bit wrap-around accumulators over the packed table; a frame is one aligned dword.
 template <int STAGE>
 __global__ __launch_bounds__(kBlock) void fir1d_cplx_resample_generic32_kernel(
     const uint32_t* __restrict__ x, typename OutTraits<STAGE>::T* __restrict__ y, int64_t n_out, int64_t width,
@@ -316,21 +238,11 @@ __global__ __launch_bounds__(kBlock) void fir1d_cplx_resample_generic32_kernel(
     if (gi >= n_out) return;
     const int64_t m = gi % out_width, r = gi / out_width;
     const int64_t j = m * D + phase;
-    const int64_t i = j / U, e = j % U;
-    const int64_t pe = (e + L / 2) % U, n = i + (e + L / 2) / U;
-    const int64_t t_lo = n - width + 1 > 0 ? n - width + 1 : 0;
-    const int64_t t_max = pe < L ? (L - 1 - pe) / U : -1;
-    const int64_t t_hi = n < t_max ? n : t_max;
-    const uint32_t* __restrict__ xf = x + r * width + n;  // tap pe + U * t meets frame xf[-t]
+    const cext::PolyWalk w = cext::poly_walk(j, U, L, width);
+    const uint32_t* __restrict__ xf = x + r * width + w.n;  // tap pe + U * t meets frame xf[-t]
     uint32_t re = 0, im = 0;
-    for (int64_t t = t_lo; t <= t_hi; ++t) {
-        const uint32_t d = xf[-t];
-        const int64_t k = pe + U * t;
-        re = dot2_acc(d, pk[2 * k], re);
-        im = dot2_acc(d, pk[2 * k + 1], im);
-    }
-    y[2 * gi] = fir::stage_out32<STAGE>(fir::round32(re, shl, frac));
-    y[2 * gi + 1] = fir::stage_out32<STAGE>(fir::round32(im, shl, frac));
+    for (int64_t t = w.t_lo; t <= w.t_hi; ++t) cext::cmac32(re, im, pk, w.pe + U * t, xf[-t]);
+    cext::store_frame32<STAGE>(y, gi, re, im, shl, frac);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -413,10 +325,10 @@ int route_of(uintptr_t x, uintptr_t y, int64_t rows, int64_t width, int64_t ow, 
              int decim, int phase, int frac, int acc_bits, int stage, int* bucket) {
     (void)y;  // y may sit at any element address on every route
     *bucket = 0;
-    const bool d2 = dot2_ok(hq, L, frac, acc_bits);
+    const bool d2 = cext::dot2_ok(hq, L, frac, acc_bits);
     if (d2 && up >= 2 && up <= kCrMaxUD && decim >= 2 && decim <= kCrMaxUD && L <= kCrMaxTaps &&
         (L + up - 1) / up <= kCrMaxNP && stage == FIR_OUT_I32 && x % 16 == 0 &&
-        (rows == 1 || width % kCrChunk == 0)) {  // every row starts as x does
+        (rows == 1 || width % kChunk == 0)) {  // every row starts as x does
         const int64_t per = (int64_t)cr_periods(decim) * up;  // output frames per workgroup
         const int64_t groups = (ow + per - 1) / per;
         // the grid is rows * groups < 2^31 workgroups; the kernel holds a group index in 32 bits
@@ -426,7 +338,7 @@ int route_of(uintptr_t x, uintptr_t y, int64_t rows, int64_t width, int64_t ow, 
         }
     }
     if (d2 && x % 4 == 0) return FIR_CRESAMPLE_GENERIC32;
-    return needs_wide(hq, L, acc_bits) ? FIR_CRESAMPLE_GENERIC128 : FIR_CRESAMPLE_GENERIC64;
+    return cext::needs_wide(hq, L, acc_bits) ? FIR_CRESAMPLE_GENERIC128 : FIR_CRESAMPLE_GENERIC64;
 }
 
 // what the calling thread's last launch() launched: every kernel goes through cext::launch_recorded
@@ -437,10 +349,10 @@ static hipError_t launch_fast_np(const void* x, void* y, int64_t rows, int64_t w
                                  int D, const Plan& pl, int frac, int acc_bits, hipStream_t s) {
     const int P = cr_periods(D);
     const int ext = pl.kmax + NP;                           // window dwords a period can read
-    const int chunks = cr_chunks(kCrChunk - 1, P, D, ext);  // lead <= 3
+    const int chunks = cr_chunks(kChunk - 1, P, D, ext);    // lead <= 3
     // never taken: cr_slots bounds U * NP, kCrMaxExt the windows
     if (U * NP > cr_slots(NP) || ext > kCrOffs || chunks > kCrMaxIt * kBlock) return hipErrorInvalidValue;
-    const int PL = (chunks * kCrChunk + D - 1) / D;  // dwords per plane
+    const int PL = (chunks * kChunk + D - 1) / D;  // dwords per plane
     TapsCr<NP> t = {};
     for (int k = 0; k < kCrOffs; ++k) t.off[k] = (uint32_t)((k % D) * PL + k / D);
     for (int q = 0; q < U; ++q) {
@@ -456,8 +368,8 @@ static hipError_t launch_fast_np(const void* x, void* y, int64_t rows, int64_t w
     const int T = tile_of(P, U);
     const int in_dwords = (D * PL + 3) & ~3;
     const uint32_t stage_bytes = (uint32_t)(T * U * 8) + 16u;
-    const size_t lds = (size_t)in_dwords * sizeof(uint32_t) + cr_phys(stage_bytes) + 4;
-    const uint32_t magic = (1u << kCrMagicShift) / (uint32_t)D + 1;
+    const size_t lds = (size_t)in_dwords * sizeof(uint32_t) + cext::phys(stage_bytes) + 4;
+    const uint32_t magic = (1u << cext::kMagicShift) / (uint32_t)D + 1;
     const int64_t groups = (ow + (int64_t)P * U - 1) / ((int64_t)P * U);
     const dim3 grid((unsigned)(rows * groups));
     if (acc_bits == 32)
@@ -492,34 +404,6 @@ static hipError_t launch_fast(int bucket, const void* x, void* y, int64_t rows, 
     }
 }
 
-template <int STAGE>
-static hipError_t launch_generic(int route, const void* x, void* y, int64_t rows, int64_t width, int64_t ow,
-                                 const int32_t* hq, int L, int U, int D, int phase, int frac, int acc_bits,
-                                 hipStream_t s) {
-    using OutT = typename OutTraits<STAGE>::T;
-    const int64_t n_out = rows * ow;
-    const int64_t blocks = (n_out + kBlock - 1) / kBlock;
-    if (blocks >= ((int64_t)1 << 31)) return hipErrorInvalidValue;
-    const dim3 grid((unsigned)blocks);
-    hipError_t e = hipSuccess;
-    std::lock_guard<std::mutex> hold(cext::g_tab_mu);  // until the launch is enqueued
-    if (route == FIR_CRESAMPLE_GENERIC32) {
-        const std::vector<uint32_t> pk = cext::pack_dot2(hq, L);
-        const uint32_t* pd = (const uint32_t*)table_locked(pk.data(), sizeof(uint32_t) * pk.size(), s, &e);
-        if (!pd) return e;
-        return launch_recorded(route, 0, fir1d_cplx_resample_generic32_kernel<STAGE>, grid, 0, s, (const uint32_t*)x,
-                               (OutT*)y, n_out, width, ow, (int64_t)U, (int64_t)D, (int64_t)phase, pd, L, 32 - acc_bits,
-                               frac);
-    }
-    const int32_t* td = (const int32_t*)table_locked(hq, sizeof(int32_t) * 2 * (size_t)L, s, &e);
-    if (!td) return e;
-    if (route == FIR_CRESAMPLE_GENERIC128)
-        return launch_recorded(route, 0, fir1d_cplx_resample_generic_kernel<STAGE, true>, grid, 0, s, (const int16_t*)x,
-                               (OutT*)y, n_out, width, ow, (int64_t)U, (int64_t)D, (int64_t)phase, td, L, frac, acc_bits);
-    return launch_recorded(route, 0, fir1d_cplx_resample_generic_kernel<STAGE, false>, grid, 0, s, (const int16_t*)x,
-                           (OutT*)y, n_out, width, ow, (int64_t)U, (int64_t)D, (int64_t)phase, td, L, frac, acc_bits);
-}
-
 int launch(const int16_t* x, int64_t rows, int64_t width, const int32_t* hq, int L, int up, int decim, int phase,
            int frac, int acc_bits, int stage, void* y, hipStream_t stream, std::string* err) {
     int64_t ow = 0;
@@ -535,7 +419,13 @@ int launch(const int16_t* x, int64_t rows, int64_t width, const int32_t* hq, int
         e = launch_fast(bucket, x, y, rows, width, ow, hq, L, up, decim, phase, frac, acc_bits, stream);
     else
         e = fir::with_stage(stage, [&](auto st) {
-            return launch_generic<st>(route, x, y, rows, width, ow, hq, L, up, decim, phase, frac, acc_bits, stream);
+            return cext::launch_generic(
+                route, FIR_CRESAMPLE_GENERIC32, FIR_CRESAMPLE_GENERIC128, fir1d_cplx_resample_generic32_kernel<st>,
+                fir1d_cplx_resample_generic_kernel<st, false>, fir1d_cplx_resample_generic_kernel<st, true>, rows * ow, hq,
+                L, frac, acc_bits, stream, [&](auto kernel, dim3 grid, const void* table, int t0, int t1) {
+                    return launch_recorded(route, 0, kernel, grid, 0, stream, x, y, rows * ow, width, ow, (int64_t)up,
+                                           (int64_t)decim, (int64_t)phase, table, L, t0, t1);
+                });
         });
     if (e != hipSuccess) return *err = std::string("fir1d cplx resample launch failed: ") + hipGetErrorString(e), FIR_EHIP;
     return FIR_OK;

@@ -6,7 +6,8 @@ libfir_cstream.so): a hash of the sources it is built from.
 the package and refuses a library built from other sources.  The sources are everything in
 ``csrc_<name>/``, its header, the headers it includes from the first library (the two header-only
 device helpers of ``csrc/`` and ``include/fir_hip.h``, the status and stage values) and every file
-of ``csrc_cext/``, the host layer and make rules the extension libraries share.
+of ``csrc_cext/``, the host layer, the device header (``cext_device.h``) and the make rules the
+extension libraries share.
 Standalone on purpose (no NumPy, no import of the package): the make rules run it as
 ``python3 _srcid_ext.py <name>``.
 """
