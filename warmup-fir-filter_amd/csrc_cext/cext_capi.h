@@ -1,5 +1,5 @@
 // cext_capi.h — the host layer behind the extern "C" boundary of an extension library
-// (capi_cdecim.hip, capi_cinterp.hip, capi_cresample.hip, capi_cstream.hip).  No library compiles
+// (capi_cdecim.hip, capi_cinterp.hip, capi_cresample.hip, capi_cstream.hip, capi_crstream.hip).  No library compiles
 // this directory on its own; each includes this header into its one capi_*.hip.
 //
 // The host-pointer entry owns, per device, one non-blocking stream and a grow-only pair of device
@@ -147,7 +147,7 @@ int host_rows(const char* lib, int device, const void* x, void* y, size_t in_byt
     return FIR_OK;
 }
 
-// The same for an entry that moves two inputs and two outputs (capi_cstream.hip: a block and its
+// The same for an entry that moves two inputs and two outputs (capi_cstream.hip, capi_crstream.hip: a block and its
 // history in, the kept frames and the next history out).  Either second pointer may be NULL: that
 // array is not moved and launch gets NULL for it.  The second array of each pair sits in the same
 // device buffer as the first, at the next multiple of 256 bytes.

@@ -1,7 +1,8 @@
 // cext_device.h — the device side that the kernel sources of the complex-tap rate-changing FIRs
 // share (fir1d_cplx_decim.hip, fir1d_cplx_interp.hip, fir1d_cplx_resample.hip,
-// fir1d_cplx_stream.hip): input staging, the polyphase LDS planes, the LDS output stage, the
-// decimating tile kernel body of cdecim and cstream, and the steps of the generic kernels.
+// fir1d_cplx_stream.hip, fir1d_cplx_rstream.hip): input staging, the polyphase LDS planes, the LDS
+// output stage, the decimating tile kernel body of cdecim and cstream, the resampling tile kernel
+// body of cresample and crstream, and the steps of the generic kernels.
 //
 // Everything here is a constexpr, a plain struct or a __device__ __forceinline__ function of
 // internal linkage.  No __global__ kernel lives here: the libraries are loaded into one process, and
@@ -237,6 +238,156 @@ __device__ __forceinline__ void decim_tile(const uint32_t* __restrict__ x, const
             __builtin_nontemporal_store(u2_a4{(uint32_t)fir::round_acc<ACC32>(re1, shl, frac),
                                               (uint32_t)fir::round_acc<ACC32>(im1, shl, frac)},
                                         reinterpret_cast<u2_a4*>(yo + 2 * (kTileT / 2)));
+    }
+}
+
+// ---- the resampling tile kernel: the hot path of cresample (HIST = false) and crstream (HIST = true).
+//
+// The decimator's input side, the interpolator's output side and the complex MAC; the work split,
+// the D input planes, the by-value tap, window and offset tables and the LDS output stage are
+// described at the top of csrc_cresample/fir1d_cplx_resample.hip.  What the two libraries differ in
+// is the library's: S, the first frame of a period's lowest window (centred for the one-shot entry,
+// causal and >= -H for the streaming one), and with HIST the frames [-H, 0) of a row, which staging
+// takes from the row's history as decim_tile does.
+constexpr int kRsInBytes = 4096;    // input bytes a workgroup keeps in flight, at least
+constexpr int kRsMinT = 256;        // the smallest tile and workgroup: one pass, one period per lane
+constexpr int kRsOutBytes = 16384;  // T = P halved while T * U * 8 exceeds this
+constexpr int kRsMaxUD = 16;        // 2 <= U, D <= 16
+constexpr int kRsMaxTaps = 128;
+constexpr int kRsMaxNP = 32;        // the largest tap bucket: ceil(L / U) of the fast path
+constexpr int kRsOffs = 64;         // window dwords a lane can address: the highest k0 + NP is 17 + 32
+
+// periods per workgroup
+__host__ __device__ constexpr int rs_periods(int D) {
+    int P = kRsMinT;
+    while (P * D * 4 < kRsInBytes) P *= 2;
+    return P;
+}
+// 16-byte chunks a workgroup of n periods stages: lead + the last period's first frame + ext, the
+// frames from there to the end of the furthest window (the highest k0 + NP)
+__host__ __device__ constexpr int rs_chunks(int lead, int n, int D, int ext) {
+    return (lead + (n - 1) * D + ext + kChunk - 1) / kChunk;
+}
+constexpr int kRsMaxExt = kRsMaxUD + 1 + kRsMaxNP;  // k0 <= D + 1
+constexpr int rs_max_chunks() {
+    int m = 0;
+    for (int D = 2; D <= kRsMaxUD; ++D) {
+        const int c = rs_chunks(kChunk - 1, rs_periods(D), D, kRsMaxExt);
+        m = c > m ? c : m;
+    }
+    return m;
+}
+constexpr int kRsMaxIt = (rs_max_chunks() + kBlock - 1) / kBlock;  // staging steps per thread
+static_assert(kRsMaxIt == 5, "staging steps");
+static_assert(kChunk * kRsMaxIt * kBlock < (1 << 14), "the magic division's range");
+static_assert(kRsMaxExt <= kRsOffs, "the offset table holds every window dword");
+
+// the tap buckets, and the one below a bucket (0 below the first)
+constexpr int kRsBuckets[] = {1, 2, 3, 4, 6, 8, 10, 12, 16, 20, 24, 28, kRsMaxNP};
+constexpr int rs_prev_bucket(int NP) {
+    int prev = 0;
+    for (const int b : kRsBuckets) {
+        if (b >= NP) break;
+        prev = b;
+    }
+    return prev;
+}
+// Dwords per tap table of bucket NP: U * NP for the largest U that can land in it.  A longest
+// sub-filter of more than prev taps has ceil(L / U) > prev, so L >= U * prev + 1 and, with L <= 128,
+// U <= 127 / prev.
+constexpr int rs_slots(int NP) {
+    const int prev = rs_prev_bucket(NP);
+    const int umax = prev < 1 || (kRsMaxTaps - 1) / prev > kRsMaxUD ? kRsMaxUD : (kRsMaxTaps - 1) / prev;
+    return umax * NP;
+}
+static_assert(rs_slots(1) == 16 && rs_slots(16) == 160 && rs_slots(kRsMaxNP) == 128, "tap table sizes");
+
+template <int NP>
+struct ResampleTaps {
+    uint32_t a[rs_slots(NP)];  // phase q, window dword w at q * NP + w: (hr, -hi) of the tap that meets it
+    uint32_t b[rs_slots(NP)];  //                                        (hi, hr); zero where no tap does
+    uint32_t k0[kRsMaxUD];     // phase q: its window's first dword, from the period's first window dword
+    uint32_t off[kRsOffs];     // window dword k of a period lies (k mod D) * PL + k / D dwords from its plane row
+};
+
+// hist: the first frame of the rows x H frames of history, or NULL for a zero one (HIST only).
+// taps is __restrict__: without it the NP = 32 kernels take 14 more SGPRs than with the body in the kernel.
+template <int NP, bool ACC32, bool HIST>
+__device__ __forceinline__ void resample_tile(const uint32_t* __restrict__ x, const uint32_t* __restrict__ hist,
+                                              int32_t* __restrict__ y, int64_t width, int64_t out_width,
+                                              uint32_t groups, int U, int D, int P, int T, int S, int ext, int H,
+                                              int PL, uint32_t magic, const ResampleTaps<NP>& __restrict__ taps,
+                                              int shl, int frac) {
+    extern __shared__ __attribute__((aligned(16))) uint32_t rs_lds[];  // D planes of PL dwords, then the output stage
+    const uint32_t tb = blockIdx.x % groups;
+    const int64_t r = blockIdx.x / groups;
+    const int64_t v0 = (int64_t)tb * P;  // first period of the workgroup
+    const int64_t m0 = v0 * U;           // ... and its first output frame
+    const int TU = T * U;                // output frames per tile
+    const int64_t left = (out_width - m0 + TU - 1) / TU;
+    const int gt = left < P / T ? (int)left : P / T;  // its tiles (the row's last workgroup: fewer)
+    const int64_t a0 = v0 * D + S;                    // its first window's first frame (< 0: outside, or history)
+    const int64_t o = a0 & ~(int64_t)(kChunk - 1);    // the first frame staged: floor to 4 frames
+    const int lead = (int)(a0 - o);                   // 0..3
+    const int nchunks = rs_chunks(lead, gt * T, D, ext);
+    const uint32_t* __restrict__ xr = x + r * width;
+
+    // ---- stage frames [o, o + 4 * nchunks) of the row in D planes; LDS dword 0 is the first window's
+    // first frame a0 (the up to 3 frames in front of it are never read)
+    u4 raw[kRsMaxIt];
+    if constexpr (HIST) {  // frames [-H, 0) are the row's history (zero for a NULL one)
+        stage_load(raw, xr, o, nchunks, width, [&](int64_t f) {
+            const uint32_t* __restrict__ hr = hist ? hist + r * H + H : nullptr;  // frame f < 0 is hr[f]
+            if (f >= 0) return f < width ? xr[f] : 0u;
+            return hr && f >= -(int64_t)H ? hr[f] : 0u;
+        });
+    } else {  // zero outside [0, width)
+        stage_load(raw, xr, o, nchunks, width, [&](int64_t f) { return f >= 0 && f < width ? xr[f] : 0u; });
+    }
+    scatter_planes(rs_lds, raw, nchunks, lead, D, PL, magic);
+    __syncthreads();
+
+    uint32_t* const outw = rs_lds + ((D * PL + 3) & ~3);
+    const int u = threadIdx.x;
+    const uint32_t vstep = (uint32_t)U * 8u;  // bytes from a period's outputs to the next period's
+    for (int g = 0; g < gt; ++g) {
+        const int64_t mg = m0 + (int64_t)g * TU;                          // the tile's first output frame
+        const int no = out_width - mg < TU ? (int)(out_width - mg) : TU;  // its output frames inside the row
+        char* const yt = reinterpret_cast<char*>(y + (r * out_width + mg) * 2);
+        const uint32_t sh = (uint32_t)(reinterpret_cast<uintptr_t>(yt) & 15u);  // the stage's first byte
+
+        // ---- lane u: the U output frames of period u of every pass (kBlock periods), into the stage
+        for (int vp = u; vp < T && vp * U < no; vp += kBlock) {
+            const uint32_t wrow = (uint32_t)(g * T + vp);  // its plane row: dword wrow * D is its first window dword
+            uint32_t b = sh + (uint32_t)vp * vstep;        // period vp, output 0
+            for (int q = 0; q < U; ++q, b += 8u) {
+                const uint32_t* __restrict__ ta = taps.a + q * NP;  // wave-uniform
+                const uint32_t* __restrict__ tq = taps.b + q * NP;
+                const uint32_t* __restrict__ oo = taps.off + taps.k0[q];
+                uint32_t re = 0, im = 0;
+                // at most 16 window dwords at a time, so that a chunk's taps and offsets fit the SGPRs
+                constexpr int NC = (NP + 15) / 16, CW = (NP + NC - 1) / NC;
+#pragma unroll
+                for (int c = 0; c < NC; ++c) {
+                    if (c) __builtin_amdgcn_sched_barrier(0);
+                    uint32_t d[CW];
+#pragma unroll
+                    for (int w = c * CW; w < (c + 1) * CW && w < NP; ++w) d[w - c * CW] = rs_lds[wrow + oo[w]];
+#pragma unroll
+                    for (int w = c * CW; w < (c + 1) * CW && w < NP; ++w) {
+                        re = dot2_acc(d[w - c * CW], ta[w], re);
+                        im = dot2_acc(d[w - c * CW], tq[w], im);
+                    }
+                }
+                outw[phys(b) >> 2] = (uint32_t)fir::round_acc<ACC32>(re, shl, frac);
+                outw[phys(b + 4u) >> 2] = (uint32_t)fir::round_acc<ACC32>(im, shl, frac);
+            }
+        }
+        __syncthreads();
+
+        // ---- the tile's output run [sh, end) of the stage, as 16-byte vectors at 16-byte addresses
+        write_run(outw, yt, sh, sh + (uint32_t)no * 8u);
+        __syncthreads();  // the next tile overwrites the stage
     }
 }
 

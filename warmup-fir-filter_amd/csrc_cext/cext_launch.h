@@ -1,9 +1,9 @@
 // cext_launch.h — the host side that the kernel sources of the complex-tap rate-changing FIRs
 // share (fir1d_cplx_decim.hip, fir1d_cplx_interp.hip, fir1d_cplx_resample.hip,
-// fir1d_cplx_stream.hip): the common head of
+// fir1d_cplx_stream.hip, fir1d_cplx_rstream.hip): the common head of
 // check(), the exactness tests behind the routes, the generic-32 tap packing, the launch record,
-// the generic kernels' tap-table cache and launch, and the host half of the decimating tile kernel
-// of cdecim and cstream.  No library compiles this directory on its own; each includes this header
+// the generic kernels' tap-table cache and launch, and the host halves of the decimating tile kernel
+// of cdecim and cstream and of the resampling tile kernel of cresample and crstream.  No library compiles this directory on its own; each includes this header
 // into its one kernel source.  The device code they share is in cext_device.h.
 //
 // Everything here has internal linkage (an unnamed namespace, `static`): the libraries are loaded
@@ -240,6 +240,111 @@ static TileGeom tile_geom(int D, int LP, int64_t rows, int64_t ow) {
     g.lds = (size_t)D * g.PL * sizeof(uint32_t);
     g.grid = dim3((unsigned)(rows * groups));
     return g;
+}
+
+// ---- the host half of cext_device.h's resampling tile kernel (cresample, crstream).
+
+// The U windows of a period.  Phase q: p the first tap, c the frame (from the period's first) that
+// tap meets, n the taps, k0 the first dword of its window counted from S, the first frame of the
+// lowest window; need: the longest sub-filter; kmax: the highest k0.
+struct RsPlan {
+    int S = 0, need = 0, kmax = 0;
+    int p[kRsMaxUD] = {}, c[kRsMaxUD] = {}, n[kRsMaxUD] = {}, k0[kRsMaxUD] = {};
+};
+
+// centre: the filter's shift in intermediate frames, L / 2 for the one-shot entry and 0 for the
+// causal streaming one.  With centre = 0, c >= 0 and n - 1 <= (L - 1) / U, so S >= -((L - 1) / U);
+// c <= D - 1 and n >= need - 1, so k0 <= D.
+static RsPlan rs_plan_of(int L, int U, int D, int phase, int centre) {
+    RsPlan pl;
+    int lo = 0;
+    bool any = false;
+    for (int q = 0; q < U; ++q) {
+        const int a = phase + centre + q * D;
+        pl.p[q] = a % U;
+        pl.c[q] = a / U;
+        pl.n[q] = pl.p[q] < L ? (L - pl.p[q] + U - 1) / U : 0;  // 0: an empty phase, its outputs are 0
+        if (!pl.n[q]) continue;
+        const int s = pl.c[q] - pl.n[q] + 1;
+        if (!any || s < lo) lo = s;
+        any = true;
+        if (pl.n[q] > pl.need) pl.need = pl.n[q];
+    }
+    pl.S = lo;
+    for (int q = 0; q < U; ++q) {
+        if (!pl.n[q]) continue;
+        pl.k0[q] = pl.c[q] - pl.n[q] + 1 - pl.S;  // >= 0
+        if (pl.k0[q] > pl.kmax) pl.kmax = pl.k0[q];
+    }
+    return pl;
+}
+
+static int rs_bucket_of(int need) {
+    for (const int b : kRsBuckets)
+        if (need <= b) return b;
+    return kRsMaxNP;
+}
+
+// go(IntTag<NP>) for the bucket NP
+template <typename Go>
+static hipError_t with_rs_bucket(int bucket, Go go) {
+    switch (bucket) {
+        case 1: return go(fir::IntTag<1>{});
+        case 2: return go(fir::IntTag<2>{});
+        case 3: return go(fir::IntTag<3>{});
+        case 4: return go(fir::IntTag<4>{});
+        case 6: return go(fir::IntTag<6>{});
+        case 8: return go(fir::IntTag<8>{});
+        case 10: return go(fir::IntTag<10>{});
+        case 12: return go(fir::IntTag<12>{});
+        case 16: return go(fir::IntTag<16>{});
+        case 20: return go(fir::IntTag<20>{});
+        case 24: return go(fir::IntTag<24>{});
+        case 28: return go(fir::IntTag<28>{});
+        default: return go(fir::IntTag<kRsMaxNP>{});
+    }
+}
+
+// the launch geometry of bucket NP at the rates U / D under a plan
+struct RsGeom {
+    int P, T, ext, PL;  // periods per workgroup and per tile, window dwords a period can read, dwords per plane
+    uint32_t magic, groups;
+    size_t lds;
+    dim3 grid;
+};
+
+// The geometry and the tap, window and offset tables of a launch; false (never taken: rs_slots
+// bounds U * NP, kRsMaxExt the windows) when the plan does not fit the tables.
+template <int NP>
+static bool rs_setup(const int32_t* hq, int U, int D, const RsPlan& pl, int64_t rows, int64_t ow, RsGeom* g,
+                     ResampleTaps<NP>* t) {
+    g->P = rs_periods(D);
+    g->ext = pl.kmax + NP;
+    const int chunks = rs_chunks(kChunk - 1, g->P, D, g->ext);  // lead <= 3
+    if (U * NP > rs_slots(NP) || g->ext > kRsOffs || chunks > kRsMaxIt * fir::kBlock) return false;
+    g->PL = (chunks * kChunk + D - 1) / D;
+    for (int k = 0; k < kRsOffs; ++k) t->off[k] = (uint32_t)((k % D) * g->PL + k / D);
+    for (int q = 0; q < U; ++q) {
+        t->k0[q] = (uint32_t)pl.k0[q];
+        for (int w = 0; w < pl.n[q]; ++w) {  // window dword w is frame S + k0 + w = c - (n - 1 - w): tap n - 1 - w
+            const int k = pl.p[q] + U * (pl.n[q] - 1 - w);
+            const int32_t hr = hq[2 * k], hi = hq[2 * k + 1];
+            const uint32_t r16 = (uint32_t)hr & 0xFFFFu, i16 = (uint32_t)hi & 0xFFFFu, ni16 = (uint32_t)(-hi) & 0xFFFFu;
+            t->a[q * NP + w] = r16 | (ni16 << 16);
+            t->b[q * NP + w] = i16 | (r16 << 16);
+        }
+    }
+    // periods per tile: the workgroup's periods, halved while the tile's outputs exceed kRsOutBytes
+    g->T = g->P;
+    while (g->T > kRsMinT && g->T * U * 8 > kRsOutBytes) g->T /= 2;
+    const int in_dwords = (D * g->PL + 3) & ~3;
+    const uint32_t stage_bytes = (uint32_t)(g->T * U * 8) + 16u;
+    g->lds = (size_t)in_dwords * sizeof(uint32_t) + phys(stage_bytes) + 4;
+    g->magic = (1u << kMagicShift) / (uint32_t)D + 1;
+    const int64_t groups = (ow + (int64_t)g->P * U - 1) / ((int64_t)g->P * U);
+    g->groups = (uint32_t)groups;
+    g->grid = dim3((unsigned)(rows * groups));
+    return true;
 }
 
 }  // namespace

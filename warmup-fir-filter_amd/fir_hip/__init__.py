@@ -11,7 +11,8 @@ Host-array entry points (NumPy in, NumPy out, synchronous):
     first use by :mod:`fir_hip.cdecim`), fir1d_fixed_rows_cplx_interp (libfir_cinterp.so, loaded on first use by
     :mod:`fir_hip.cinterp`), fir1d_fixed_rows_cplx_resample (libfir_cresample.so, loaded on first use by
     :mod:`fir_hip.cresample`), fir1d_fixed_rows_cplx_decim_block (libfir_cstream.so, loaded on first use by
-    :mod:`fir_hip.cstream`), fir1d_fixed_rows_multi,
+    :mod:`fir_hip.cstream`), fir1d_fixed_rows_cplx_resample_block (libfir_crstream.so, loaded on first use by
+    :mod:`fir_hip.crstream`), fir1d_fixed_rows_multi,
     fir1d_fixed_rows_sharded, fir2d_fixed, fir2d_ideal, fir1d_ideal_rows, compare_metrics, restore_u8, and the stage drivers' image batches
     fir1d_fixed_images_multi / fir1d_ideal_images_multi (page-locked staging: host_empty)
 Device entry points (torch tensors on a HIP device, enqueued on the current stream):
@@ -39,6 +40,7 @@ __all__ = [
     "interp_out_width", "fir1d_fixed_rows_interp", "resample_out_width", "fir1d_fixed_rows_resample",
     "fir1d_fixed_rows_cplx", "fir1d_fixed_rows_cplx_decim", "fir1d_fixed_rows_cplx_interp", "Launch", "launch_log",
     "kernel_census", "fir1d_fixed_rows_cplx_resample", "fir1d_fixed_rows_cplx_decim_block",
+    "fir1d_fixed_rows_cplx_resample_block",
 ]
 
 IN_U8, IN_I16 = 0, 1
@@ -649,6 +651,19 @@ def fir1d_fixed_rows_cplx_decim_block(x: np.ndarray, hist, hq, decim: int, phase
     from . import cstream
 
     return cstream.fir1d_fixed_rows_cplx_decim_block(x, hist, hq, decim, phase, frac_bits, acc_bits, out_stage, device)
+
+
+def fir1d_fixed_rows_cplx_resample_block(x: np.ndarray, hist, hq, up: int, decim: int, phase: int = 0,
+                                         frac_bits: int = 12, acc_bits: int = 32, out_stage: int = OUT_I32,
+                                         device: int = 0):
+    """One block of a stream through the causal U/D resampling complex-tap FIR, behind the history
+    that precedes it; returns (y, hist_out, next_phase):
+    :func:`fir_hip.crstream.fir1d_fixed_rows_cplx_resample_block`, whose extension library
+    (libfir_crstream.so) is loaded on first use."""
+    from . import crstream
+
+    return crstream.fir1d_fixed_rows_cplx_resample_block(x, hist, hq, up, decim, phase, frac_bits, acc_bits, out_stage,
+                                                         device)
 
 
 def fir1d_fixed_rows_sharded(x: np.ndarray, hq, frac_bits: int = 12, acc_bits: int = 32,

@@ -1,5 +1,5 @@
 """The loader the extension libraries' ctypes modules share (:mod:`fir_hip.cdecim`,
-:mod:`fir_hip.cinterp`, :mod:`fir_hip.cresample`, :mod:`fir_hip.cstream`): one :class:`Ext` per library, built from its name
+:mod:`fir_hip.cinterp`, :mod:`fir_hip.cresample`, :mod:`fir_hip.cstream`, :mod:`fir_hip.crstream`): one :class:`Ext` per library, built from its name
 and its EXPORTS table.  It loads ``libfir_<name>.so`` on first use, binds and checks the exports,
 refuses a library built from other sources, and holds what the modules' ``route``,
 ``last_launch`` and host-array entries have in common.  Constructing one loads nothing.
@@ -82,7 +82,7 @@ class Ext:
         return r, bucket.value
 
     def route4(self, entry: str, addrs, rows, width, hq, rates, frac_bits, acc_bits, out_stage) -> tuple[int, int]:
-        """:meth:`route` for an entry that takes four addresses (fir_cplx_stream_route: x, hist_in, y
+        """:meth:`route` for an entry that takes four addresses (fir_cplx_stream_route, fir_cplx_rstream_route: x, hist_in, y
         and hist_out, 0 for NULL)."""
         h = _taps_cplx_i32(hq)
         bucket = ctypes.c_int(0)

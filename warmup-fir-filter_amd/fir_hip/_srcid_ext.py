@@ -1,5 +1,5 @@
 """The source id of an extension library (libfir_cdecim.so, libfir_cinterp.so, libfir_cresample.so,
-libfir_cstream.so): a hash of the sources it is built from.
+libfir_cstream.so, libfir_crstream.so): a hash of the sources it is built from.
 
 ``make -C warmup-fir-filter_amd/csrc_<name>`` embeds it (``-DFIR_<NAME>_BUILD_ID``, exported as
 ``fir_<name>_build_id()``); the loader (:mod:`fir_hip._ext`) recomputes it from the sources beside
@@ -47,7 +47,7 @@ def source_id(name: str, pkg: Path = PKG) -> str | None:
 
 if __name__ == "__main__":
     if len(sys.argv) != 2:
-        sys.exit("usage: _srcid_ext.py <name>   (cdecim, cinterp, cresample or cstream)")
+        sys.exit("usage: _srcid_ext.py <name>   (cdecim, cinterp, cresample, cstream or crstream)")
     sid = source_id(sys.argv[1])
     if sid is None:
         sys.exit(f"libfir_{sys.argv[1]} sources not found")
