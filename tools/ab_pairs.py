@@ -7,7 +7,8 @@ equal the first's.  Printed per workload: every round's times, then per library 
 the median of its per-round difference to library 0 with the count of rounds it was faster.
 Workloads: i16 = BASELINE configs[1] (2^28 int16 -> int32, 5-tap sharpen); u8 = the reference's
 own u8 -> sat-u8 path (a1: 2^28 u8 in 4096-sample rows, 5-tap sharpen); bank = the 4-filter 3-tap
-u8 bank (h_coeff_3tap_map) over the same rows.
+u8 bank (h_coeff_3tap_map) over the same rows; cplx = BASELINE configs[2] (2^27 complex int16 ->
+complex int32, 3-tap simple low-pass, two interleaved channels).
 
 Usage: python tools/ab_pairs.py <rounds> <workloads, comma list> <lib0> <lib1> [lib2 ...]
 """
@@ -20,6 +21,7 @@ import numpy as np
 import torch
 
 SHARPEN5 = (-256, -1024, 6656, -1024, -256)
+SIMPLE_LP3 = (1024, 2048, 1024)
 BANK3 = (1365, 1365, 1365, 1024, 2048, 1024, -4096, 0, 4096, -512, 5120, -512)
 BATCH = 50
 
@@ -34,10 +36,15 @@ def main():
     report = {}
     for wl in wls:
         n = 1 << 28
+        ch = 1
         if wl == "i16":
             x = torch.from_numpy(rng.integers(-32768, 32768, n, dtype=np.int16)).to(dev)
             ys = [torch.empty(n, dtype=torch.int32, device=dev) for _ in libs]
             in_dt, rows, width, stage, h, L, F = 1, 1, n, 1, SHARPEN5, 5, 1
+        elif wl == "cplx":
+            x = torch.from_numpy(rng.integers(-32768, 32768, n, dtype=np.int16)).to(dev)
+            ys = [torch.empty(n, dtype=torch.int32, device=dev) for _ in libs]
+            in_dt, rows, width, stage, h, L, F, ch = 1, 1, n // 2, 1, SIMPLE_LP3, 3, 1, 2
         else:
             width = 4096
             x = torch.from_numpy(rng.integers(0, 256, n, dtype=np.uint8)).to(dev)
@@ -51,7 +58,7 @@ def main():
         def run(i, k):
             for _ in range(k):
                 rc = libs[i].fir1d_fixed_rows_multi_dev(vp(x.data_ptr()), ci(in_dt), ctypes.c_int64(rows),
-                                                        ctypes.c_int64(width), ci(1), hc, ci(L), ci(F), ci(12),
+                                                        ctypes.c_int64(width), ci(ch), hc, ci(L), ci(F), ci(12),
                                                         ci(32), ci(stage), vp(ys[i].data_ptr()), vp(s.cuda_stream))
                 assert rc == 0, rc
 

@@ -1,7 +1,7 @@
 // fir_micro.hip — A/B microbenchmark for the hot 1-D kernel (dev tool, not the product).
 //
 // Times variants of fir1d_reg_kernel<int16, int32, 5 taps> (chunks per wave U, NT flags,
-// persistent grid) interleaved round-robin in ONE process (guide §5.4 rule 24), next to
+// persistent grid, threads per block) interleaved round-robin in ONE process (guide §5.4 rule 24), next to
 // "widen copy" kernels that move the same bytes (2 B in, 4 B out per sample) with no math,
 // which bound what the FIR can reach on this traffic mix.  Every FIR variant is checked
 // against a CPU evaluation at ~270k sampled positions plus both ends.
@@ -197,16 +197,16 @@ struct Variant {
     std::vector<float> us;
 };
 
-template <int U, int FLAGS>
+template <int U, int FLAGS, int BLK = kBlock>
 static void launch_fir(const int16_t* x, int32_t* y, int64_t n, hipStream_t s, int pblocks) {
     RowGeom g{n, 0, 0, 1};
     TapsN<5> t;
     for (int k = 0; k < 5; ++k) t.h[0][k] = kTaps[k];
     pack_taps(t);
     int64_t ntiles, blocks;
-    reg_launch_geometry<int16_t, U, FLAGS>(n, pblocks, &ntiles, &blocks);
-    hipLaunchKernelGGL((fir1d_reg_kernel<int16_t, FIR_OUT_I32, 5, 1, U, FLAGS>), dim3((unsigned)blocks),
-                       dim3(kBlock), 0, s, x, y, g, t, 0, 12, ntiles);
+    reg_launch_geometry<int16_t, U, FLAGS, BLK>(n, pblocks, &ntiles, &blocks);
+    hipLaunchKernelGGL((fir1d_reg_kernel<int16_t, FIR_OUT_I32, 5, 1, U, FLAGS, 1, BLK>), dim3((unsigned)blocks),
+                       dim3(BLK), 0, s, x, y, g, t, 0, 12, ntiles);
 }
 
 template <int U, int FLAGS>
@@ -259,11 +259,15 @@ int main(int argc, char** argv) {
     hipStream_t st;
     CK(hipStreamCreate(&st));
 
+    // the library's flag word for the headline at 2 / 4 / 8 waves per block (4 / 8 / 16 KiB of
+    // output per block; profiles/store_geometry), each twice so that the order cannot favour one
+    constexpr int kLib = kDot2 | kAcc32 | kCoal | kNtStore | kEdgeDword | kMasked;
     std::vector<Variant> vs = {
-        {"fir U1 coal ntst (lib)", true, launch_fir<1, kDot2 | kAcc32 | kCoal | kNtStore>, 0, {}},
-        {"fir U1 coal ntst edw", true, launch_fir<1, kDot2 | kAcc32 | kCoal | kNtStore | kEdgeDword>, 0, {}},
-        {"fir U1 coal ntst (lib) b", true, launch_fir<1, kDot2 | kAcc32 | kCoal | kNtStore>, 0, {}},
-        {"fir U1 coal ntst edw b", true, launch_fir<1, kDot2 | kAcc32 | kCoal | kNtStore | kEdgeDword>, 0, {}},
+        {"fir b256", true, launch_fir<1, kLib, 256>, 0, {}},
+        {"fir b128 (lib)", true, launch_fir<1, kLib, 128>, 0, {}},
+        {"fir b512", true, launch_fir<1, kLib, 512>, 0, {}},
+        {"fir b256 b", true, launch_fir<1, kLib, 256>, 0, {}},
+        {"fir b128 (lib) b", true, launch_fir<1, kLib, 128>, 0, {}},
         {"copy U1 coal (LDS)", false, launch_copy_coal, 0, {}},
     };
 
@@ -277,7 +281,7 @@ int main(int argc, char** argv) {
         CK(hipStreamSynchronize(st));
         CK(hipMemcpy(hy.data(), dy, n * 4, hipMemcpyDeviceToHost));
         int64_t bad = 0, checked = 0;
-        for (int64_t i = 0; i < n; i += (i < 4096 || i > n - 4096) ? 1 : 997) {
+        for (int64_t i = 0; i < n; i += (i < 3 * 4096 || i > n - 3 * 4096) ? 1 : 997) {
             ++checked;
             if (hy[i] != ref_at(hx, i)) {
                 if (bad < 3) fprintf(stderr, "%s: mismatch at %lld: %d vs %d\n", v.name.c_str(), (long long)i, hy[i], ref_at(hx, i));

@@ -6,6 +6,8 @@
 // copies are checked against the CPU.
 //
 // Build: make -C tools/microbench     Run: tools/microbench/stream_micro [rounds]
+// STREAM_SET=geometry runs the store-geometry tables instead (rows per wave x row assignment x
+// block size x policy, write-only and as widen copies; profiles/store_geometry).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -272,6 +274,52 @@ __global__ __launch_bounds__(BLOCK) void write_pat(int32_t* __restrict__ y) {
             st16<POL>(dst + k * 64 * G + lane * G + g, u32x4{(uint32_t)lane, (uint32_t)k, (uint32_t)g, 1u});
 }
 
+// ---- store geometry (profiles/store_geometry) -------------------------------------------
+// Whole 1 KiB rows, R per wave, with the rows of a block's WPB = BLOCK / 64 waves assigned
+// A=0 adjacent (wave w writes rows wR .. wR+R-1, the FIR's kCoal shape) or A=1 block-strided (wave w
+// writes rows w, w + WPB, ...: the block's k-th store instructions cover WPB consecutive KiB).
+// A block writes WPB * R KiB either way, so R, BLOCK and A separate rows per wave, bytes per block
+// and row adjacency.  R = 1 is the same kernel under both assignments.
+template <int R, int A, int POL, int BLOCK>
+__global__ __launch_bounds__(BLOCK) void write_geo(int32_t* __restrict__ y) {
+    constexpr int WPB = BLOCK / 64;
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    u32x4* dst = reinterpret_cast<u32x4*>(y) + (int64_t)blockIdx.x * (WPB * R * 64);
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+        const int row = A ? r * WPB + w : w * R + r;
+        st16<POL>(dst + row * 64 + lane, u32x4{(uint32_t)lane, (uint32_t)r, (uint32_t)w, 1u});
+    }
+}
+// The widen twin, 16-byte loads (1 KiB per load instruction), two rows out per wave.  G=0 adjacent
+// rows (widen_pat<0, 0>); G=1 split tile: lanes 0-31 load vectors 32w .. of the block's span and
+// lanes 32-63 vectors 32 WPB + 32w .., so the wave's own LDS transpose yields span rows w and
+// WPB + w with no barrier (the block still loads one contiguous WPB KiB); G=2 contiguous 1 KiB
+// loads, block-wide LDS and one s_barrier, then rows w and WPB + w.
+template <int G, int POL, int BLOCK>
+__global__ __launch_bounds__(BLOCK) void widen_geo(const int16_t* __restrict__ x, int32_t* __restrict__ y) {
+    constexpr int WPB = BLOCK / 64;
+    __shared__ u32x4 sb[BLOCK];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const u32x4* src = reinterpret_cast<const u32x4*>(x) + (int64_t)blockIdx.x * BLOCK;
+    u32x4* dst = reinterpret_cast<u32x4*>(y) + (int64_t)blockIdx.x * (2 * BLOCK);
+    const int v = G == 1 ? (lane < 32 ? 32 * w + lane : 32 * WPB + 32 * w + (lane - 32)) : 64 * w + lane;
+    sb[64 * w + lane] = __builtin_nontemporal_load(src + v);
+    if constexpr (G == 2) {
+        __syncthreads();
+    } else {
+        __builtin_amdgcn_wave_barrier();
+        asm volatile("" ::: "memory");
+    }
+    const u32x2* s2 = reinterpret_cast<const u32x2*>(sb);
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+        const int row = G == 0 ? 2 * w + i : i * WPB + w;         // of the block's 2 WPB output rows
+        const int from = G == 2 ? row : 2 * w + i;                // LDS row (512 B of int16) it comes from
+        st16<POL>(dst + row * 64 + lane, widen_lo(s2[from * 64 + lane]));
+    }
+}
+
 // ---------------------------------------------------------------------------------------
 struct Bufs {
     int16_t* x;
@@ -323,6 +371,15 @@ template <int H, int P, int POL, int BLOCK>
 void l_wdpat(const Bufs& b, hipStream_t s) {
     hipLaunchKernelGGL((widen_pat<H, P, POL, BLOCK>), dim3((unsigned)(b.n / (H ? 256 : 512) / (BLOCK / 64))),
                        dim3(BLOCK), 0, s, b.x, b.y);
+}
+
+template <int R, int A, int POL, int BLOCK>
+void l_wgeo(const Bufs& b, hipStream_t s) {
+    hipLaunchKernelGGL((write_geo<R, A, POL, BLOCK>), dim3((unsigned)(b.n / 4 / (BLOCK * R))), dim3(BLOCK), 0, s, b.y);
+}
+template <int G, int POL, int BLOCK>
+void l_wdgeo(const Bufs& b, hipStream_t s) {
+    hipLaunchKernelGGL((widen_geo<G, POL, BLOCK>), dim3((unsigned)(b.n / 8 / BLOCK)), dim3(BLOCK), 0, s, b.x, b.y);
 }
 
 template <int D, bool NT, int BPC>
@@ -686,6 +743,27 @@ int main(int argc, char** argv) {
         {"read reg K1 b256", l_read_reg<1, 256>, rd, false, {}},
         {"write nt rows R1", l_wpat<0, 1, 1, 256>, wr, false, {}},
     };
+    // STREAM_SET=geometry: the store-geometry tables (profiles/store_geometry) instead of the ladder
+    // above: write-only 1 GiB over rows per wave x row assignment x block size x policy, then the
+    // widen copies with 16-byte loads in each geometry next to the two existing widen shapes.
+    if (getenv("STREAM_SET") && std::string(getenv("STREAM_SET")) == "geometry") {
+        vs.clear();
+#define WGEO(POL, PN, BLOCK)                                                               \
+    vs.push_back({"w R1 " PN " b" #BLOCK, l_wgeo<1, 0, POL, BLOCK>, wr, false, {}});          \
+    vs.push_back({"w R2 adjacent " PN " b" #BLOCK, l_wgeo<2, 0, POL, BLOCK>, wr, false, {}}); \
+    vs.push_back({"w R2 strided " PN " b" #BLOCK, l_wgeo<2, 1, POL, BLOCK>, wr, false, {}});
+#define WGEO4(POL, PN) WGEO(POL, PN, 64) WGEO(POL, PN, 128) WGEO(POL, PN, 256) WGEO(POL, PN, 512)
+        WGEO4(1, "nt") WGEO4(0, "plain") WGEO4(2, "sc0sc1")
+#define DGEO(POL, PN, BLOCK)                                                                  \
+    vs.push_back({"widen adjacent " PN " b" #BLOCK, l_wdgeo<0, POL, BLOCK>, rw, true, {}});     \
+    vs.push_back({"widen split " PN " b" #BLOCK, l_wdgeo<1, POL, BLOCK>, rw, true, {}});        \
+    vs.push_back({"widen barrier " PN " b" #BLOCK, l_wdgeo<2, POL, BLOCK>, rw, true, {}});
+        DGEO(1, "nt", 128) DGEO(1, "nt", 256) DGEO(1, "nt", 512)
+        DGEO(2, "sc0sc1", 128) DGEO(2, "sc0sc1", 256) DGEO(2, "sc0sc1", 512)
+        vs.push_back({"widen rows nt", l_wdpat<0, 0, 1, 256>, rw, true, {}});
+        vs.push_back({"widen half row nt", l_wdpat<1, 0, 1, 256>, rw, true, {}});
+        vs.push_back({"read reg K1 b256", l_read_reg<1, 256>, rd, false, {}});
+    }
     // correctness of every widen variant (sampled)
     std::vector<int32_t> hy(b.n);
     for (auto& v : vs) {

@@ -614,7 +614,8 @@ __device__ __forceinline__ void ragged_prepare(const uint32_t (&Wd)[NW], const i
 
 // The tiles tile, tile + stride, ... below ntiles of one buffer (wave-uniform tile); output
 // plane f (g.total samples) at yf[f].
-template <typename InT, int STAGE, int L, int CH, int U, int FLAGS, int F>
+// WPB: waves per block (sizes the kCoal LDS rows).
+template <typename InT, int STAGE, int L, int CH, int U, int FLAGS, int F, int WPB = kBlock / kWave>
 __device__ __forceinline__ void fir1d_reg_body(const InT* __restrict__ x, typename OutTraits<STAGE>::T* const (&yf)[F],
                                                const RowGeom& g, const TapsN<L, F>& taps, int shl, int frac,
                                                int64_t ntiles, int64_t tile, int64_t stride) {
@@ -818,7 +819,7 @@ __device__ __forceinline__ void fir1d_reg_body(const InT* __restrict__ x, typena
                     }
                     if constexpr (COAL) {
                         if (vb + (u + 1) * kWave <= nvec) {  // wave-uniform: the whole chunk is full
-                            __shared__ u32x4 sbuf[kBlock * VEC / 4];
+                            __shared__ u32x4 sbuf[WPB * kWave * VEC / 4];
                             u32x4* wb = sbuf + (threadIdx.x - lane) * (VEC / 4);
 #pragma unroll
                             for (int i = 0; i < VEC / 4; ++i)
@@ -862,19 +863,20 @@ __device__ __forceinline__ void fir1d_reg_body(const InT* __restrict__ x, typena
     }
 }
 
-template <typename InT, int STAGE, int L, int CH, int U, int FLAGS, int F = 1>
-__global__ __launch_bounds__(kBlock) void fir1d_reg_kernel(const InT* __restrict__ x,
-                                                           typename OutTraits<STAGE>::T* __restrict__ y,
-                                                           RowGeom g, TapsN<L, F> taps, int shl, int frac,
-                                                           int64_t ntiles) {
-    constexpr int WPB = kBlock / kWave;
+// BLK: threads per block.  The int16 -> int32 kernels run 128 (kRegBlock, fir1d_reg_impl.h): a block
+// then writes 4 KiB, the size at which write streams run fastest (profiles/store_geometry).
+template <typename InT, int STAGE, int L, int CH, int U, int FLAGS, int F = 1, int BLK = kBlock>
+__global__ __launch_bounds__(BLK) void fir1d_reg_kernel(const InT* __restrict__ x,
+                                                        typename OutTraits<STAGE>::T* __restrict__ y, RowGeom g,
+                                                        TapsN<L, F> taps, int shl, int frac, int64_t ntiles) {
+    constexpr int WPB = BLK / kWave;
     const int64_t stride = (FLAGS & kPersist) ? (int64_t)gridDim.x * WPB : ntiles;
     const int64_t bpos = (FLAGS & kXcd) ? xcd_block(blockIdx.x, gridDim.x) : (int64_t)blockIdx.x;
     typename OutTraits<STAGE>::T* yf[F];  // plane f at y + f * total
 #pragma unroll
     for (int f = 0; f < F; ++f) yf[f] = y + f * g.total;
-    fir1d_reg_body<InT, STAGE, L, CH, U, FLAGS, F>(x, yf, g, taps, shl, frac, ntiles, bpos * WPB + (threadIdx.x >> 6),
-                                                   stride);
+    fir1d_reg_body<InT, STAGE, L, CH, U, FLAGS, F, WPB>(x, yf, g, taps, shl, frac, ntiles,
+                                                        bpos * WPB + (threadIdx.x >> 6), stride);
 }
 
 // Several images (buffers of rows) in ONE launch, the same F filters over each: the wave tiles
@@ -907,12 +909,12 @@ __global__ __launch_bounds__(kBlock) void fir1d_reg_batch_kernel(RegBatch b, Tap
 }
 
 // Tiles and grid for a launch of fir1d_reg_kernel<.., U, FLAGS>.
-template <typename InT, int U, int FLAGS>
+template <typename InT, int U, int FLAGS, int BLK = kBlock>
 inline void reg_launch_geometry(int64_t total, int persist_blocks, int64_t* ntiles, int64_t* blocks) {
     constexpr int VEC = 4 * InTraits<InT>::kPerDword;
     const int64_t vecs = (total + VEC - 1) / VEC;
     *ntiles = (vecs + (int64_t)kWave * U - 1) / ((int64_t)kWave * U);
-    const int64_t need = (*ntiles + (kBlock / kWave) - 1) / (kBlock / kWave);
+    const int64_t need = (*ntiles + (BLK / kWave) - 1) / (BLK / kWave);
     *blocks = (FLAGS & kPersist) ? (need < persist_blocks ? need : persist_blocks) : need;
 }
 

@@ -29,6 +29,16 @@ namespace fir {
 // A fused bank keeps the same flags: an XCD-major block order and a persistent grid measured
 // slower or equal (profiles/r04/bank_ab.txt).
 constexpr int kRegFlags = kCoal | kNtStore | kEdgeDword;
+// Block size of fir1d_reg_kernel.  int16 -> int32 (the headline, the two-channel complex config and
+// the kHalo segment kernel): 128 threads, so that a block's kCoal rows are 4 KiB of output.  Write
+// streams of whole 1 KiB rows run fastest at 4 KiB per block whatever the rows per wave (1 GiB:
+// 159.5 us at 1 row x 4 waves, 163.1 at 2 x 2, against 182.1 at 2 x 4 and 183.2 at 1 x 2), and which
+// rows of the block a wave writes does not matter (profiles/store_geometry/stream_geometry.txt).  The
+// FIR follows: 241.9 vs 245.5 us (headline) and 242.6 vs 247.2 us (complex) in interleaved pairs
+// against 256 threads; 512 threads 252.7 us (profiles/store_geometry/).  Every other configuration
+// keeps kBlock: their blocks were not measured at another size.
+template <typename InT, int STAGE>
+constexpr int kRegBlock = sizeof(InT) == 2 && STAGE == FIR_OUT_I32 ? 128 : kBlock;
 constexpr int kPersistBlocks = 2048;
 
 template <typename InT>
@@ -64,7 +74,8 @@ static hipError_t launch_reg_flags(const void* x, void* y, int64_t rows, int64_t
     TapsN<L, F> t;
     if (!make_taps<L, F, FL>(t, hq, frac)) return hipErrorInvalidValue;
     int64_t ntiles = 0, blocks = 0;
-    reg_launch_geometry<InT, kRegU<InT, F>, FL>(total, kPersistBlocks, &ntiles, &blocks);
+    constexpr int BLK = kRegBlock<InT, STAGE>;
+    reg_launch_geometry<InT, kRegU<InT, F>, FL, BLK>(total, kPersistBlocks, &ntiles, &blocks);
     // One int16 filter keeps the masked pair compiled in even where it cannot run: that code
     // layout is faster in every one of 12 interleaved pairs in one process (headline 244.98 vs
     // 246.02 us median, profiles/r06/ab_pairs_single_filter.txt).  u8 filters and banks drop it:
@@ -73,8 +84,8 @@ static hipError_t launch_reg_flags(const void* x, void* y, int64_t rows, int64_t
     constexpr int FM = F == 1 && sizeof(InT) == 2 ? kMasked : 0;
     if constexpr (F == 1) {
         if (hl != nullptr || hr != nullptr) {
-            FIR_LAUNCH((fir1d_reg_kernel<InT, STAGE, L, CH, kRegU<InT, F>, FL | kHalo | FM, F>), dim3((unsigned)blocks),
-                               dim3(kBlock), 0, stream, (const InT*)x, (OutT*)y, g, t, 32 - acc_bits, frac, ntiles);
+            FIR_LAUNCH((fir1d_reg_kernel<InT, STAGE, L, CH, kRegU<InT, F>, FL | kHalo | FM, F, BLK>), dim3((unsigned)blocks),
+                               dim3(BLK), 0, stream, (const InT*)x, (OutT*)y, g, t, 32 - acc_bits, frac, ntiles);
             return hipGetLastError();
         }
     } else if (hl != nullptr || hr != nullptr) {
@@ -82,11 +93,11 @@ static hipError_t launch_reg_flags(const void* x, void* y, int64_t rows, int64_t
     }
     if (!g.aligned) {  // rows straddle vectors: one signal with seams patched (u8 stage), else masked
         constexpr int FX = STAGE == FIR_OUT_U8_SAT && CH == 1 ? kRagged : kMasked;
-        FIR_LAUNCH((fir1d_reg_kernel<InT, STAGE, L, CH, kRegU<InT, F>, FL | FX, F>), dim3((unsigned)blocks),
-                           dim3(kBlock), 0, stream, (const InT*)x, (OutT*)y, g, t, 32 - acc_bits, frac, ntiles);
+        FIR_LAUNCH((fir1d_reg_kernel<InT, STAGE, L, CH, kRegU<InT, F>, FL | FX, F, BLK>), dim3((unsigned)blocks),
+                           dim3(BLK), 0, stream, (const InT*)x, (OutT*)y, g, t, 32 - acc_bits, frac, ntiles);
         return hipGetLastError();
     }
-    FIR_LAUNCH((fir1d_reg_kernel<InT, STAGE, L, CH, kRegU<InT, F>, FL | FM, F>), dim3((unsigned)blocks), dim3(kBlock), 0,
+    FIR_LAUNCH((fir1d_reg_kernel<InT, STAGE, L, CH, kRegU<InT, F>, FL | FM, F, BLK>), dim3((unsigned)blocks), dim3(BLK), 0,
                        stream, (const InT*)x, (OutT*)y, g, t, 32 - acc_bits, frac, ntiles);
     return hipGetLastError();
 }
